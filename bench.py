@@ -7,6 +7,16 @@ of the hot path over one resident batch: removeCounterResets + rollup grid
 evaluation over all series (the RunParallel seam, eval.go:1927/1968).
 
   python bench.py --gpus N --steps K --warmup W [--series S] [--aggr sum]
+                  [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints the result line.
+--dump-outputs DIR then writes what the last timed step computed as
+DIR/<name>.npy (a fixed seeded sample of rows where the output is large;
+NaN points are zeroed and marked in <name>_nonfinite.npy), so two builds
+can be compared output for output: the inputs depend on the arguments
+alone.  --full adds the secondary measurements, which take
+runs of their own: cpu_baseline, cold_query and grouped (each null in the
+line of a plain run).
 
 N>1 runs under torchrun (one rank per GPU over RCCL); series are sharded by
 seriesID with a full-size shard per rank (weak scaling); the
@@ -16,9 +26,10 @@ the [groups x grid] partial matrices.
 
 Prints ONE JSON line from rank 0 (driver contract), including:
   roofline: achieved = algorithmic bytes/launch / HIP-event kernel time
-            (16 B/sample read + 8 B/grid-point write)
-  cpu_baseline: the CPU oracle (kind "port") on this box's host cores over a
-            bounded subsample of the same workload
+            of the timed steps (16 B/sample read + 8 B/grid-point write,
+            SURVEY.md §8d)
+  cpu_baseline (--full): the CPU oracle (kind "port") on the host cores
+            over a bounded subsample of the same workload
 """
 import argparse
 import json
@@ -47,6 +58,11 @@ def parse_args():
     ap.add_argument("--aggr", type=str, default="none",
                     choices=["none", "sum", "min", "max", "avg", "count"])
     ap.add_argument("--groups", type=int, default=10_000)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs to DIR/*.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the secondary measurements (CPU baseline, "
+                         "cold query, grouped config 3)")
     ap.add_argument("--cpu-baseline-target-s", type=float, default=15.0)
     ap.add_argument("--skip-cpu-baseline", action="store_true")
     ap.add_argument("--skip-cold", action="store_true",
@@ -191,6 +207,50 @@ def grouped_probe(args, engine, ts, vals, offsets, end):
     }
 
 
+DUMP_MAX_BYTES = 16 << 20  # per matrix; its float32 mask adds half of it
+
+
+def dump_outputs(dirname, batch, last, n_grid, grouped):
+    """Write what the last timed step returned to its caller as
+    DIR/<name>.npy.  The ungrouped step leaves its [series x grid] matrix
+    on the device, where a caller reads it with fetch_out; it is far larger
+    than the budget, so a fixed seeded sample of its rows is kept (the same
+    rows on every run, in ascending order).  Grouped steps return the
+    [groups x grid] values and counts.
+
+    A rollup has NaN wherever a grid point has no value (too few samples in
+    its window), so every matrix is written as two finite arrays:
+    <name>.npy (float64, 0.0 at the points without a finite value) and
+    <name>_nonfinite.npy (float32: 0 finite, 1 NaN, 2 +Inf, 3 -Inf)."""
+    os.makedirs(dirname, exist_ok=True)
+
+    def save(name, a):
+        np.save(os.path.join(dirname, name + ".npy"), a)
+
+    def save_matrix(name, a):
+        keep = DUMP_MAX_BYTES // (a.shape[1] * 8)
+        if a.shape[0] > keep:
+            rows = np.random.default_rng(8428).choice(a.shape[0], size=keep,
+                                                      replace=False)
+            a = a[np.sort(rows)]
+        a = np.ascontiguousarray(a, dtype=np.float64)
+        kind = np.zeros(a.shape, dtype=np.float32)
+        kind[np.isnan(a)] = 1
+        kind[a == np.inf] = 2
+        kind[a == -np.inf] = 3
+        save(name, np.where(kind == 0, a, 0.0))
+        save(name + "_nonfinite", kind)
+
+    if grouped:
+        save_matrix("aggr_values", last["out"])
+        save_matrix("aggr_counts", last["counts"])
+    else:
+        out, _ = batch.fetch_out(batch.n_series, n_grid)
+        save_matrix("rollup_values", out)
+    # exact in float64: far below 2**53
+    save("samples_scanned", np.array([last["scanned"]], dtype=np.float64))
+
+
 def main():
     args = parse_args()
     rank = int(os.environ.get("RANK", "0"))
@@ -227,15 +287,19 @@ def main():
     batch = engine.SeriesBatch(ts, vals, offsets, group_ids=gids,
                                n_groups=args.groups if grouped else 0)
 
+    last = {}  # what the latest step handed its caller (--dump-outputs)
+
     def one_step():
-        out, counts, _ = batch.exec(plan, download=grouped)
+        out, counts, scanned = batch.exec(plan, download=grouped)
         if grouped and distributed:
             import torch.distributed as dist
             tv = torch.from_numpy(out).cuda(local_rank)
             tc = torch.from_numpy(counts).cuda(local_rank)
             dist.all_reduce(tv)  # SUM (sum/avg/count); one 19 MB exchange
             dist.all_reduce(tc)
-            engine.aggr_finalize(args.aggr, tv.cpu().numpy(), tc.cpu().numpy())
+            counts = tc.cpu().numpy()
+            out = engine.aggr_finalize(args.aggr, tv.cpu().numpy(), counts)
+        last.update(out=out, counts=counts, scanned=scanned)
         return engine.last_kernel_ms()
 
     # warmup
@@ -284,16 +348,19 @@ def main():
     if os.environ.get("VMGPU_TRAFFIC_BYTES"):
         traffic = float(os.environ["VMGPU_TRAFFIC_BYTES"])
 
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, batch, last, n_grid, grouped)
+
     result = None
     if rank == 0:
         cb = None
-        if not args.skip_cpu_baseline and world == 1:
+        if args.full and not args.skip_cpu_baseline and world == 1:
             cb = cpu_baseline(args, plan._c, ts, vals, offsets, n_grid)
         cold = None
-        if not args.skip_cold and world == 1 and not grouped:
+        if args.full and not args.skip_cold and world == 1 and not grouped:
             cold = cold_query(args, engine, plan, ts, vals, offsets)
         grouped_info = None
-        if not args.skip_grouped and world == 1 and not grouped:
+        if args.full and not args.skip_grouped and world == 1 and not grouped:
             grouped_info = grouped_probe(args, engine, ts, vals, offsets, end)
         workload = (f"{args.func}(metric[5m])[1h:15s] over 1M series x 240 samples"
                     if not grouped else
