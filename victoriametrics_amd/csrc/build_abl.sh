@@ -24,4 +24,14 @@ build_one pipe_mw6 -DVMGPU_PIPE_MINWAVES=6 &
 build_one pipe_u2 -DVMGPU_PIPE_UNROLL=2 &
 build_one pipe_scat -DVMGPU_PIPE_SCATTER &
 wait
+# instruction-count cuts, one off at a time (all four are on by default),
+# and all four off (the kernel before them, plus the ungated scalar
+# bookkeeping and the NaN-value fixes described at the gates in vmgpu.hip)
+build_one pipe_nosent -DVMGPU_PIPE_SENTINEL=0 &
+build_one pipe_nohacc -DVMGPU_PIPE_HINT_ACC=0 &
+build_one pipe_nodtfast -DVMGPU_PIPE_DT_FAST=0 &
+build_one pipe_nopmaxskip -DVMGPU_PIPE_SKIP_PMAX=0 &
+build_one pipe_nocuts -DVMGPU_PIPE_SENTINEL=0 -DVMGPU_PIPE_HINT_ACC=0 \
+  -DVMGPU_PIPE_DT_FAST=0 -DVMGPU_PIPE_SKIP_PMAX=0 &
+wait
 echo "ablation libs built"

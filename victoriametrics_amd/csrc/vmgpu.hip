@@ -40,7 +40,46 @@
 
 #include "devalloc.h"
 #include "rollup_device.h"
+#include "vm_div1e3.h"
 #include "../../include/vmgpu.h"
+
+/* Instruction-count cuts of the pipe kernel, each behind its own gate so
+ * build_abl.sh can A/B them one at a time (-DVMGPU_PIPE_<X>=0 turns one
+ * off).  None changes an output bit.
+ *
+ * Not behind a gate, because they are not cuts but what the cuts needed to
+ * stay inside the kernel's 89 VGPRs: the samples-scanned total is a
+ * wave-uniform scalar instead of a lane-0 value reduced by shuffles, and
+ * ts0 / the sample density are moved to scalar registers.
+ *
+ * Separate from the cuts, two NaN-VALUE fixes towards the reference change
+ * results for series that hold an ordinary (non-stale) NaN sample, in every
+ * kernel that shares the code: eval_rate_fused treats a NaN previous sample
+ * as "no previous value" (rollupDerivFast tests isnan(prevValue)), and the
+ * four removeCounterResets scans treat a NaN element as a clamp boundary
+ * (`values[i] < values[i-1]` is false on either side of a NaN, where the
+ * fmax prefix-max used to overwrite the NaN with its predecessor).  The
+ * -D...=0 builds therefore differ from the kernel before this work by
+ * exactly these fixes.
+ *   SENTINEL  sentinel-padded series slab: the boundary probe and the rate
+ *             evaluator drop their edge clamps
+ *   HINT_ACC  the probe hint is one f64 accumulator advanced per round
+ *   DT_FAST   dt / 1e3 by the exact multiply+fma sequence of vm_div1e3.h
+ *             for series whose span fits 31 bits
+ *   SKIP_PMAX removeCounterResets skips the segmented prefix-max when the
+ *             monotonic clamp is provably the identity */
+#ifndef VMGPU_PIPE_SENTINEL
+#define VMGPU_PIPE_SENTINEL 1
+#endif
+#ifndef VMGPU_PIPE_HINT_ACC
+#define VMGPU_PIPE_HINT_ACC 1
+#endif
+#ifndef VMGPU_PIPE_DT_FAST
+#define VMGPU_PIPE_DT_FAST 1
+#endif
+#ifndef VMGPU_PIPE_SKIP_PMAX
+#define VMGPU_PIPE_SKIP_PMAX 1
+#endif
 
 #define WAVE 64
 #define BLOCK_THREADS 256
@@ -136,6 +175,70 @@ static VM_DEV int vm_ub_hint_fast(const int64_t* ts, int n, int64_t seek, int g)
   return r;
 }
 
+/* a wave-uniform 64-bit value moved to scalar registers */
+static VM_DEV int64_t vm_uniform_i64(int64_t x) {
+  uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)x);
+  uint32_t hi = __builtin_amdgcn_readfirstlane((uint32_t)((uint64_t)x >> 32));
+  return (int64_t)(((uint64_t)hi << 32) | lo);
+}
+
+/* Sentinel records of the pipe kernel's pair-interleaved slab: two 16-byte
+ * {t, v} records in front of sample 0 (t = INT64_MIN) and two behind sample
+ * count-1 (t = INT64_MAX), v = 0 in all four. */
+#define VM_SENT_RECS 2
+#define VM_SENT_BYTES (2 * VM_SENT_RECS * 16)
+
+/* vm_ub_hint_fast for the sentinel-padded slab (stride 2, ts = sample 0).
+ * With the hint clamped to [0, n] the four probed records g-2 .. g+1 all
+ * exist, so there is one base address, four constant-offset reads and no
+ * edge terms: "x == 0 or ts[x-1] <= seek" holds at x == 0 because
+ * ts[-1] = INT64_MIN, "x == n or ts[x] > seek" at x == n because
+ * ts[n] = INT64_MAX, and the candidates g+1 > n and g-1 < 0 fail on the
+ * same records (INT64_MAX <= seek resp. INT64_MIN > seek are false).  A
+ * seek of INT64_MAX itself ends in the binary-search fallback like any other
+ * miss.  Result identical to vm_upper_bound<2>. */
+static VM_DEV int vm_ub_hint_sent(const int64_t* ts, int n, int64_t seek, int g) {
+  g = g < 0 ? 0 : (g > n ? n : g);
+  const int64_t* b = ts + (g - 2) * 2;
+  int64_t t_m2 = b[0];
+  int64_t t_m1 = b[2];
+  int64_t t_0 = b[4];
+  int64_t t_p1 = b[6];
+  /* All four records exist, so the reads are safe in any order and at any
+   * lane mask.  The gfx950 build reads ts[g-1] and ts[g] as one ds_read2_b64
+   * and fetches the outer two only for the lanes whose hint missed. */
+  bool ok_g = (t_m1 <= seek) & (t_0 > seek);
+  bool ok_p1 = (t_0 <= seek) & (t_p1 > seek);
+  bool ok_m1 = (t_m2 <= seek) & (t_m1 > seek);
+  int r = ok_g ? g : (ok_p1 ? g + 1 : (ok_m1 ? g - 1 : -1));
+  if (__any(r < 0)) {
+    if (r < 0) r = vm_upper_bound<2>(ts, n, seek);
+  }
+  return r;
+}
+
+/* pipe-kernel probe: the sentinel form when the slab is padded */
+static VM_DEV int vm_ub_pipe(const int64_t* ts, int n, int64_t seek, int g) {
+#if VMGPU_PIPE_SENTINEL
+  return vm_ub_hint_sent(ts, n, seek, g);
+#else
+  return vm_ub_hint_fast<2>(ts, n, seek, g);
+#endif
+}
+
+/* removeCounterResets clamp shortcut.  The monotonic clamp
+ * x[k] = fmax(fin[k], x[k-1]) over a segment returns fin unchanged when
+ * every non-boundary element already has fmax(fin[k], fin[k-1]) == fin[k]
+ * bit for bit (induction over the segment: x[k-1] == fin[k-1]).  This is the
+ * per-element violation test against the UNCLAMPED predecessor p: a NaN on
+ * either side, a smaller value, or an equal compare with different bits
+ * (+0.0 / -0.0, where fmax may return either) all count as violations and
+ * keep the full prefix-max path. */
+static VM_DEV bool vm_clamp_violates(double x, double p) {
+  return !(x >= p) ||
+         (x == p && __double_as_longlong(x) != __double_as_longlong(p));
+}
+
 static VM_DEV void vm_atomic_min_f64(double* addr, double val) {
   unsigned long long* p = (unsigned long long*)addr;
   unsigned long long old = __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -216,6 +319,23 @@ static __host__ __device__ inline size_t vm_jbuf_bytes(int32_t mode,
   if (mode == 2) return a2;            /* J u16 over [-dg, n_grid) */
   if (mode == 1) return a2;            /* J u16 over [0, n_grid) */
   return 0;
+}
+
+/* Per-wave LDS of the wave and pipe kernels without the boundary cache:
+ * chunk_wave 16-byte sample slots + 256 B scratch.  The pipe kernel's slab
+ * also carries the sentinel records (VM_SENT_BYTES: 32 B in front of sample
+ * 0, 32 B of room behind the last slot for a full-length series).  The
+ * kernel carves and the host sizing (launch LDS and the jbuf fit) all go
+ * through here. */
+static __host__ __device__ inline size_t vm_wave_slab_bytes(int32_t chunk_wave,
+                                                            bool pipe) {
+  size_t b = (size_t)chunk_wave * 16 + 256;
+#if VMGPU_PIPE_SENTINEL
+  if (pipe) b += VM_SENT_BYTES;
+#else
+  (void)pipe;
+#endif
+  return b;
 }
 
 struct KIO {
@@ -366,7 +486,9 @@ static __device__ int load_rcr_fused_wave(const int64_t* g_ts, const double* g_v
       c = cn;
     }
     double fin = v + mycorr;
-    bool bnd = isfirst || gap;
+    /* a NaN element keeps its value and restarts the running max, as the
+     * reference's `values[i] < values[i-1]` test does on either side of it */
+    bool bnd = isfirst || gap || vm_isnan(fin);
     double x = fin;
     int f = bnd ? 1 : 0;
     if (lane == 0 && !bnd) x = fmax(x, prev_fin);
@@ -441,16 +563,30 @@ static __device__ void rcr_scan_wave(int64_t* d_ts, double* d_vals, int count,
     double fin = v + mycorr;
     /* monotonic clamp (rollup.go:952-956) = segmented prefix max; a gap
      * element keeps its raw value and is exempt (the Go `continue`). */
-    bool bnd = isfirst || gap;
+    /* a NaN element keeps its value and restarts the running max, as the
+     * reference's `values[i] < values[i-1]` test does on either side of it */
+    bool bnd = isfirst || gap || vm_isnan(fin);
     double x = fin;
-    int f = bnd ? 1 : 0;
-    if (lane == 0 && !bnd) x = fmax(x, prev_fin);
-    for (int dlt = 1; dlt < WAVE; dlt <<= 1) {
-      double xo = __shfl_up(x, dlt);
-      int fo = __shfl_up(f, dlt);
-      if (lane >= dlt) {
-        if (!f) x = fmax(x, xo);
-        f = f | fo;
+#if VMGPU_PIPE_SKIP_PMAX
+    /* clamp shortcut (vm_clamp_violates); lanes past the series end feed
+     * nothing that is stored or carried */
+    double pfin = __shfl_up(fin, 1);
+    if (lane == 0) pfin = prev_fin;
+    const bool clamp_needed =
+        __ballot(active && !bnd && vm_clamp_violates(fin, pfin)) != 0;
+#else
+    const bool clamp_needed = true;
+#endif
+    if (clamp_needed) {
+      int f = bnd ? 1 : 0;
+      if (lane == 0 && !bnd) x = fmax(x, prev_fin);
+      for (int dlt = 1; dlt < WAVE; dlt <<= 1) {
+        double xo = __shfl_up(x, dlt);
+        int fo = __shfl_up(f, dlt);
+        if (lane >= dlt) {
+          if (!f) x = fmax(x, xo);
+          f = f | fo;
+        }
       }
     }
     if (active) d_vals[k * STR] = x;
@@ -716,13 +852,36 @@ struct __align__(16) vm_tv {
   double v;
 };
 
-template <int STR = 1>
+/* SENT: ts/vals point into the pipe kernel's sentinel-padded slab and
+ * 0 <= i <= j <= count, so the three record indices i-1, i, j-1 lie in
+ * [-1, count] and need no clamp.  Whenever one of them lands on a sentinel
+ * record the selects below already discard what was read there:
+ *   i == 0      record i-1 is a front sentinel; has_prev is false (i > 0)
+ *   i == count  record i is a back sentinel; has_prev is false (i < count)
+ *               and j == count forces n == 0, so the result is NaN
+ *   j == 0      record j-1 is a front sentinel; i == 0 forces n == 0 and
+ *               has_prev false, so the result is NaN
+ * (the clamped form read some in-range record in these cases and discarded
+ * it the same way).
+ * dt32 (wave-uniform): the series spans less than 2^31 ms, so every dt whose
+ * slope is used — a difference of two of its timestamps, j-1 >= i-1 — is in
+ * [0, 2^31): the low words give it exactly and vm_div1e3_small() equals the
+ * true division.  Discarded slopes may be garbage on either path. */
+template <int STR = 1, bool SENT = false>
 static VM_DEV double eval_rate_fused(const KPlan& p, const SeriesWindow& sw,
                                      const int64_t* ts, const double* vals,
-                                     int count, int i, int j, int64_t t_start) {
-  int im1 = i - 1 < 0 ? 0 : i - 1;
-  int ii = i < count - 1 ? i : (count - 1 < 0 ? 0 : count - 1);
-  int jm1 = j - 1 < 0 ? 0 : j - 1;
+                                     int count, int i, int j, int64_t t_start,
+                                     bool dt32 = false) {
+  int im1, ii, jm1;
+  if constexpr (SENT) {
+    im1 = i - 1;
+    ii = i;
+    jm1 = j - 1;
+  } else {
+    im1 = i - 1 < 0 ? 0 : i - 1;
+    ii = i < count - 1 ? i : (count - 1 < 0 ? 0 : count - 1);
+    jm1 = j - 1 < 0 ? 0 : j - 1;
+  }
   double v_prevc, v_first, v_end;
   int64_t t_prevc, t_first, t_end_s;
   if constexpr (STR == 2 && !VMGPU_PIPE_NO_TV) {
@@ -744,14 +903,44 @@ static VM_DEV double eval_rate_fused(const KPlan& p, const SeriesWindow& sw,
     t_end_s = ts[jm1 * STR];
   }
   int n = j - i;
+  /* a NaN previous sample counts as "no previous value", as in the
+   * reference, whose prevValue uses NaN for exactly that */
   bool has_prev = (i < count) && (i > 0) &&
-                  (t_prevc > t_start - sw.max_prev_interval);
+                  (t_prevc > t_start - sw.max_prev_interval) &&
+                  !vm_isnan(v_prevc);
   double pv = has_prev ? v_prevc : v_first;
   int64_t ptm = has_prev ? t_prevc : t_first;
-  double slope = (v_end - pv) / ((double)(t_end_s - ptm) / 1e3);
-  double res_prev = (n == 0) ? 0.0 : slope;
-  double res_nop = (n <= 1) ? vm_dnan() : slope;
-  return has_prev ? res_prev : res_nop;
+  /* unsigned subtraction: a discarded slot may pair a sentinel timestamp
+   * with a sample's, which would overflow a signed difference */
+  const int64_t dt64 = (int64_t)((uint64_t)t_end_s - (uint64_t)ptm);
+  double secs;
+#if VMGPU_PIPE_DT_FAST
+  if (dt32) {
+    int32_t dt = (int32_t)((uint32_t)t_end_s - (uint32_t)ptm);
+    secs = vm_div1e3_small((double)dt);
+  } else {
+    secs = (double)dt64 / 1e3;
+  }
+#else
+  secs = (double)dt64 / 1e3;
+#endif
+  double slope = (v_end - pv) / secs;
+  /* has_prev ? (n == 0 ? 0 : slope) : (n <= 1 ? NaN : slope), folded into
+   * one predicate and one alternative (both alternatives have a zero low
+   * word, so the select is on the high word only) */
+  bool use_slope = (has_prev & (n != 0)) | (n > 1);
+  double alt = has_prev ? 0.0 : vm_dnan();
+  return use_slope ? slope : alt;
+}
+
+/* the pipe kernel's evaluator: pair-interleaved slab, sentinel-padded when
+ * VMGPU_PIPE_SENTINEL */
+static VM_DEV double eval_rate_pipe(const KPlan& p, const SeriesWindow& sw,
+                                    const int64_t* ts, const double* vals,
+                                    int count, bool dt32, int i, int j,
+                                    int64_t t_start) {
+  return eval_rate_fused<2, VMGPU_PIPE_SENTINEL != 0>(p, sw, ts, vals, count,
+                                                      i, j, t_start, dt32);
 }
 
 template <int FUNC_CT>
@@ -810,7 +999,7 @@ __global__ __launch_bounds__(BLOCK_THREADS) void rollup_wave_kernel(KPlan p, KIO
   const int wave_in_block = threadIdx.x / WAVE;
   const int lane = threadIdx.x % WAVE;
   const size_t jbuf_bytes = vm_jbuf_bytes(p.jbuf_mode, p.jbuf_elems);
-  const size_t wave_bytes = (size_t)p.chunk_wave * 16 + 256 + jbuf_bytes;
+  const size_t wave_bytes = vm_wave_slab_bytes(p.chunk_wave, false) + jbuf_bytes;
   int64_t* lts = (int64_t*)(smem + (size_t)wave_in_block * wave_bytes);
   double* lvs = (double*)(smem + (size_t)wave_in_block * wave_bytes +
                           (size_t)p.chunk_wave * 8);
@@ -1225,23 +1414,39 @@ static __device__ void rcr_scan_col_pairs(int64_t* d_ts, double* d_vals,
     }
     double fin0 = v0 + mc0;
     double fin1 = v1 + mc1;
-    bool f0 = isfirst0 || gap0;
-    bool f1 = gap1;
+    /* a NaN element keeps its value and restarts the running max, as the
+     * reference's `values[i] < values[i-1]` test does on either side of it */
+    bool f0 = isfirst0 || gap0 || vm_isnan(fin0);
+    bool f1 = gap1 || vm_isnan(fin1);
     double x0 = fin0, x1 = fin1;
-    if (lane == 0 && !f0) x0 = fmax(x0, prev_fin);
-    double pm = f1 ? x1 : fmax(x0, x1);
-    int pf = (f0 || f1) ? 1 : 0;
-    for (int dlt = 1; dlt < WAVE; dlt <<= 1) {
-      double pmo = __shfl_up(pm, dlt);
-      int pfo = __shfl_up(pf, dlt);
-      if (lane >= dlt) {
-        if (!pf) pm = fmax(pm, pmo);
-        pf |= pfo;
+#if VMGPU_PIPE_SKIP_PMAX
+    /* clamp shortcut (vm_clamp_violates): one neighbour shuffle + ballot;
+     * elements past the series end sit above every active one and feed
+     * nothing that is stored or carried, so they are left out */
+    double pf0 = __shfl_up(fin1, 1);
+    if (lane == 0) pf0 = prev_fin;
+    const bool clamp_needed =
+        __ballot((a0 && !f0 && vm_clamp_violates(fin0, pf0)) ||
+                 (a1 && !f1 && vm_clamp_violates(fin1, fin0))) != 0;
+#else
+    const bool clamp_needed = true;
+#endif
+    if (clamp_needed) {
+      if (lane == 0 && !f0) x0 = fmax(x0, prev_fin);
+      double pm = f1 ? x1 : fmax(x0, x1);
+      int pf = (f0 || f1) ? 1 : 0;
+      for (int dlt = 1; dlt < WAVE; dlt <<= 1) {
+        double pmo = __shfl_up(pm, dlt);
+        int pfo = __shfl_up(pf, dlt);
+        if (lane >= dlt) {
+          if (!pf) pm = fmax(pm, pmo);
+          pf |= pfo;
+        }
       }
+      double inc_m = __shfl_up(pm, 1);
+      if (lane > 0 && !f0) x0 = fmax(x0, inc_m);
+      if (!f1) x1 = fmax(x1, x0);
     }
-    double inc_m = __shfl_up(pm, 1);
-    if (lane > 0 && !f0) x0 = fmax(x0, inc_m);
-    if (!f1) x1 = fmax(x1, x0);
     if (a0) d_vals[k0 * STR] = x0;
     if (a1) d_vals[k1 * STR] = x1;
     corr = cc;
@@ -1353,23 +1558,39 @@ static VM_DEV int rcr_scan_pairs(const int64_t* t0a, const int64_t* t1a,
     double fin1 = v1 + mc1;
     /* monotonic clamp = segmented prefix max; boundary elements (series
      * start / staleness gaps) keep their value and start a new segment */
-    bool f0 = isfirst0 || gap0;
-    bool f1 = gap1;
+    /* a NaN element keeps its value and restarts the running max, as the
+     * reference's `values[i] < values[i-1]` test does on either side of it */
+    bool f0 = isfirst0 || gap0 || vm_isnan(fin0);
+    bool f1 = gap1 || vm_isnan(fin1);
     double x0 = fin0, x1 = fin1;
-    if (lane == 0 && !f0) x0 = fmax(x0, prev_fin);
-    double pm = f1 ? x1 : fmax(x0, x1);
-    int pf = (f0 || f1) ? 1 : 0;
-    for (int dlt = 1; dlt < WAVE; dlt <<= 1) {
-      double pmo = __shfl_up(pm, dlt);
-      int pfo = __shfl_up(pf, dlt);
-      if (lane >= dlt) {
-        if (!pf) pm = fmax(pm, pmo);
-        pf |= pfo;
+#if VMGPU_PIPE_SKIP_PMAX
+    /* clamp shortcut (vm_clamp_violates): one neighbour shuffle + ballot;
+     * elements past the series end sit above every active one and feed
+     * nothing that is stored or carried, so they are left out */
+    double pf0 = __shfl_up(fin1, 1);
+    if (lane == 0) pf0 = prev_fin;
+    const bool clamp_needed =
+        __ballot((a0 && !f0 && vm_clamp_violates(fin0, pf0)) ||
+                 (a1 && !f1 && vm_clamp_violates(fin1, fin0))) != 0;
+#else
+    const bool clamp_needed = true;
+#endif
+    if (clamp_needed) {
+      if (lane == 0 && !f0) x0 = fmax(x0, prev_fin);
+      double pm = f1 ? x1 : fmax(x0, x1);
+      int pf = (f0 || f1) ? 1 : 0;
+      for (int dlt = 1; dlt < WAVE; dlt <<= 1) {
+        double pmo = __shfl_up(pm, dlt);
+        int pfo = __shfl_up(pf, dlt);
+        if (lane >= dlt) {
+          if (!pf) pm = fmax(pm, pmo);
+          pf |= pfo;
+        }
       }
+      double inc_m = __shfl_up(pm, 1); /* exclusive incoming (lane 0 unused) */
+      if (lane > 0 && !f0) x0 = fmax(x0, inc_m);
+      if (!f1) x1 = fmax(x1, x0);
     }
-    double inc_m = __shfl_up(pm, 1); /* exclusive incoming (lane 0 unused) */
-    if (lane > 0 && !f0) x0 = fmax(x0, inc_m);
-    if (!f1) x1 = fmax(x1, x0);
     if (a0) d_vals[k0 * 2] = x0;
     if (a1) d_vals[k1 * 2] = x1;
     corr = cc;
@@ -1403,17 +1624,41 @@ void rollup_pipe_kernel(KPlan p, KIO io) {
   const int wave_in_block = threadIdx.x / WAVE;
   const int lane = threadIdx.x % WAVE;
   const size_t jbuf_bytes = vm_jbuf_bytes(p.jbuf_mode, p.jbuf_elems);
-  const size_t wave_bytes = (size_t)p.chunk_wave * 16 + 256 + jbuf_bytes;
+  const size_t slab_bytes = vm_wave_slab_bytes(p.chunk_wave, true);
+  const size_t wave_bytes = slab_bytes + jbuf_bytes;
   /* PAIR-interleaved series slab: sample k = 16-byte {t, v} at offset 16k
    * (stride template parameter STR=2 on every accessor) — the eval
    * gathers fetch one b128 LDS read per boundary role instead of two
-   * scattered b64 reads */
-  int64_t* lts = (int64_t*)(smem + (size_t)wave_in_block * wave_bytes);
-  double* lvs = (double*)(smem + (size_t)wave_in_block * wave_bytes + 8);
+   * scattered b64 reads.
+   * Sentinel padding (VMGPU_PIPE_SENTINEL): lts points at sample 0, which
+   * sits VM_SENT_RECS records into the wave's region.  Records -2 and -1
+   * hold t = INT64_MIN and are written once per wave; records count and
+   * count+1 hold t = INT64_MAX and are rewritten for every series once its
+   * count is final (they reach 32 B past slot chunk_wave-1 for a
+   * full-length series).  v = 0 in all four.  The probe and the rate
+   * evaluator index records -2 .. count+1 without clamps; everything else
+   * (staging, compaction, scan, scrape interval) sees an ordinary slab
+   * through the shifted base.  Per wave: [front 32 B][chunk_wave x 16 B]
+   * [back 32 B][scratch 256 B][jbuf]. */
+#if VMGPU_PIPE_SENTINEL
+  char* wave_base = smem + (size_t)wave_in_block * wave_bytes + VM_SENT_RECS * 16;
+#else
+  char* wave_base = smem + (size_t)wave_in_block * wave_bytes;
+#endif
+  int64_t* lts = (int64_t*)wave_base;
+  double* lvs = (double*)(wave_base + 8);
   double* lscratch = (double*)(smem + (size_t)wave_in_block * wave_bytes +
-                               (size_t)p.chunk_wave * 16);
+                               slab_bytes - 256);
   uint16_t* jbuf = (uint16_t*)(smem + (size_t)wave_in_block * wave_bytes +
-                               (size_t)p.chunk_wave * 16 + 256);
+                               slab_bytes);
+#if VMGPU_PIPE_SENTINEL
+  /* front sentinels: lanes 0-3 write the four 8-byte words of records -2
+   * and -1 (made visible by the first phase barrier below) */
+  if (lane < 2 * VM_SENT_RECS)
+    lts[lane - 2 * VM_SENT_RECS] = (lane & 1) ? 0 : INT64_MIN;
+#endif
+  /* wave-uniform running total (only uniform values are added), so it
+   * lives in scalar registers; lane 0 publishes it at the end */
   uint64_t scanned = 0;
   const uint32_t wave_id = blockIdx.x * WAVES_PER_BLOCK + wave_in_block;
   const uint32_t wave_stride = gridDim.x * WAVES_PER_BLOCK;
@@ -1586,6 +1831,12 @@ void rollup_pipe_kernel(KPlan p, KIO io) {
         }
       }
     }
+#if VMGPU_PIPE_SENTINEL
+    /* back sentinels behind the now-final count (count <= chunk_wave, so
+     * they stay inside the slab's back room) */
+    if (lane < 2 * VM_SENT_RECS)
+      lts[count * 2 + lane] = (lane & 1) ? 0 : INT64_MAX;
+#endif
     wave_ds_sync();
 
 #ifdef VMGPU_PIPE_ABL_STAGE
@@ -1615,15 +1866,36 @@ void rollup_pipe_kernel(KPlan p, KIO io) {
     }
 #endif
     SeriesWindow sw = series_window(p, si);
-    if (lane == 0) scanned += (uint64_t)count;
+    scanned += (uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane(count);
 
     double idx_per_ms = 0.0;
     int64_t ts0 = 0;
+    /* dt32_series: every dt of this series fits 31 bits (see
+     * eval_rate_fused).  A scalar: the dt path is one branch per series —
+     * the jbuf loops below are built for the 31-bit path only, and the rare
+     * wider series (span of 2^31 ms, 24.8 days, or more) is evaluated by
+     * the two-probe loop behind them with the i64 conversion and the true
+     * division.  With count <= 1 no slope is ever used. */
+    bool dt32_series = true;
     if (count > 1) {
       ts0 = lts[0];
       int64_t span_ms = lts[(count - 1) * 2] - ts0;
       idx_per_ms = span_ms > 0 ? (double)(count - 1) / (double)span_ms : 0.0;
+      dt32_series = __builtin_amdgcn_readfirstlane(
+                 (int)(span_ms >= 0 && span_ms < ((int64_t)1 << 31))) != 0;
     }
+    /* hint advance per 64-point round (VMGPU_PIPE_HINT_ACC): the hint
+     * (te - ts0) * idx_per_ms is carried as an f64 accumulator.  It only
+     * steers the probe — the result is verified against the slab and falls
+     * back to the binary search otherwise — so its rounding is free. */
+    /* ts0 and the density come out of LDS reads, so the compiler keeps them
+     * (and everything derived from them) in vector registers although they
+     * are wave-uniform; moving them to scalar registers frees those VGPRs */
+    ts0 = vm_uniform_i64(ts0);
+    idx_per_ms = __longlong_as_double(
+        vm_uniform_i64(__double_as_longlong(idx_per_ms)));
+    [[maybe_unused]] const double hint_step =
+        (double)((int64_t)WAVE * p.step) * idx_per_ms;
     /* emit: GROUPED folds the aggregate switch in with the per-series
      * group row hoisted out of the point loop; the ungrouped build is a
      * plain coalesced row store (no per-point branch, no switch). */
@@ -1666,7 +1938,9 @@ void rollup_pipe_kernel(KPlan p, KIO io) {
     const int64_t t_step_wave = (int64_t)WAVE * p.step;
     bool done = false;
     if constexpr (FUNC_CT == VMF_RATE || FUNC_CT == VMF_DERIV_FAST) {
-      if (scat_dg > 0) {
+      const bool dt32 = VMGPU_PIPE_DT_FAST != 0;
+      const bool dt_ok = dt32_series || !dt32;
+      if (scat_dg > 0 && dt_ok) {
         /* scatter-J eval: J was built during staging; no seeks at all. */
         int gs = lane;
         int64_t te_s = p.start + (int64_t)lane * p.step;
@@ -1677,7 +1951,7 @@ void rollup_pipe_kernel(KPlan p, KIO io) {
           emit(gs, (j > 0 && j <= count) ? lvs[(j - 1) * 2] : 0.0);
           (void)i;
 #else
-          emit(gs, eval_rate_fused<2>(p, sw, lts, lvs, count, i, j,
+          emit(gs, eval_rate_pipe(p, sw, lts, lvs, count, dt32, i, j,
                                       te_s - sw.window));
 #endif
         }
@@ -1685,7 +1959,7 @@ void rollup_pipe_kernel(KPlan p, KIO io) {
       }
       int dg64 = (sw.window > 0 && p.step > 0 && sw.window % p.step == 0)
                      ? (int)(sw.window / p.step) : 0;
-      if (!done && p.jbuf_mode >= 1 &&
+      if (!done && dt_ok && p.jbuf_mode >= 1 &&
           (size_t)p.n_grid * 2 <= vm_jbuf_bytes(p.jbuf_mode, p.jbuf_elems) &&
           dg64 > 0 && count <= 65535) {
         if (dg64 < WAVE) {
@@ -1697,13 +1971,19 @@ void rollup_pipe_kernel(KPlan p, KIO io) {
           int j_prev = 0;
           int g = lane;
           int64_t te = p.start + (int64_t)lane * p.step;
+#if VMGPU_PIPE_HINT_ACC
+          double hacc = (double)(te - ts0) * idx_per_ms;
+#endif
           for (int r = 0; r * WAVE < p.n_grid;
                r++, g += WAVE, te += t_step_wave) {
             bool act = g < p.n_grid;
+#if VMGPU_PIPE_HINT_ACC
+            int gj = (int)hacc + 1;
+            hacc += hint_step;
+#else
             int gj = (int)((double)(te - ts0) * idx_per_ms) + 1;
-            int j_cur = act
-                            ? vm_ub_hint_fast<2>(lts, count, te, gj)
-                            : count;
+#endif
+            int j_cur = act ? vm_ub_pipe(lts, count, te, gj) : count;
             int i;
             int i_same = __shfl(j_cur, lane - dg64);
             int i_prev = __shfl(j_prev, lane + WAVE - dg64);
@@ -1711,14 +1991,14 @@ void rollup_pipe_kernel(KPlan p, KIO io) {
             if (r == 0 && lane < dg64) {
               int64_t t_start = te - sw.window;
               int gi = (int)((double)(t_start - ts0) * idx_per_ms) + 1;
-              i = vm_ub_hint_fast<2>(lts, count, t_start, gi);
+              i = vm_ub_pipe(lts, count, t_start, gi);
             }
             if (act) {
 #ifdef VMGPU_PIPE_ABL_NO_EVAL
               emit(g, (j_cur > 0 && j_cur <= count) ? lvs[(j_cur - 1) * 2] : 0.0);
               (void)i;
 #else
-              emit(g, eval_rate_fused<2>(p, sw, lts, lvs, count, i, j_cur,
+              emit(g, eval_rate_pipe(p, sw, lts, lvs, count, dt32, i, j_cur,
                                          te - sw.window));
 #endif
             }
@@ -1733,20 +2013,32 @@ void rollup_pipe_kernel(KPlan p, KIO io) {
           int gf = lane;
           int64_t te = p.start + (int64_t)lane * p.step;
           const int fill_full = (p.n_grid / WAVE) * WAVE;
+#if VMGPU_PIPE_HINT_ACC
+          double hacc = (double)(te - ts0) * idx_per_ms;
+#endif
           for (; gf < fill_full; gf += WAVE, te += t_step_wave) {
+#if VMGPU_PIPE_HINT_ACC
+            int gj = (int)hacc + 1;
+            hacc += hint_step;
+#else
             int gj = (int)((double)(te - ts0) * idx_per_ms) + 1;
+#endif
 #ifdef VMGPU_PIPE_WALK_PROBE
             jbuf[gf] = (uint16_t)vm_ub_hint<2>(lts, count, te, gj);
 #else
-            jbuf[gf] = (uint16_t)vm_ub_hint_fast<2>(lts, count, te, gj);
+            jbuf[gf] = (uint16_t)vm_ub_pipe(lts, count, te, gj);
 #endif
           }
           if (gf < p.n_grid) {
+#if VMGPU_PIPE_HINT_ACC
+            int gj = (int)hacc + 1;
+#else
             int gj = (int)((double)(te - ts0) * idx_per_ms) + 1;
+#endif
 #ifdef VMGPU_PIPE_WALK_PROBE
             jbuf[gf] = (uint16_t)vm_ub_hint<2>(lts, count, te, gj);
 #else
-            jbuf[gf] = (uint16_t)vm_ub_hint_fast<2>(lts, count, te, gj);
+            jbuf[gf] = (uint16_t)vm_ub_pipe(lts, count, te, gj);
 #endif
           }
         }
@@ -1760,12 +2052,12 @@ void rollup_pipe_kernel(KPlan p, KIO io) {
           int64_t t_start = t_end - sw.window;
           int j = jbuf[g];
           int gi = (int)((double)(t_start - ts0) * idx_per_ms) + 1;
-          int i = vm_ub_hint_fast<2>(lts, count, t_start, gi);
+          int i = vm_ub_pipe(lts, count, t_start, gi);
 #ifdef VMGPU_PIPE_ABL_NO_EVAL
           emit(g, (j > 0 && j <= count) ? lvs[(j - 1) * 2] : 0.0);
           (void)i;
 #else
-          emit(g, eval_rate_fused<2>(p, sw, lts, lvs, count, i, j, t_start));
+          emit(g, eval_rate_pipe(p, sw, lts, lvs, count, dt32, i, j, t_start));
 #endif
         }
         /* main eval: full lane-blocks (no per-point exec masking), then one
@@ -1782,7 +2074,7 @@ void rollup_pipe_kernel(KPlan p, KIO io) {
             emit(g, (j > 0 && j <= count) ? lvs[(j - 1) * 2] : 0.0);
             (void)i;
 #else
-            emit(g, eval_rate_fused<2>(p, sw, lts, lvs, count, i, j,
+            emit(g, eval_rate_pipe(p, sw, lts, lvs, count, dt32, i, j,
                                        te - sw.window));
 #endif
           }
@@ -1793,7 +2085,7 @@ void rollup_pipe_kernel(KPlan p, KIO io) {
             emit(g, (j > 0 && j <= count) ? lvs[(j - 1) * 2] : 0.0);
             (void)i;
 #else
-            emit(g, eval_rate_fused<2>(p, sw, lts, lvs, count, i, j,
+            emit(g, eval_rate_pipe(p, sw, lts, lvs, count, dt32, i, j,
                                        te - sw.window));
 #endif
           }
@@ -1803,21 +2095,23 @@ void rollup_pipe_kernel(KPlan p, KIO io) {
       }
     }
     if (!done) {
-      /* correctness fallback only (per-series window not a step multiple —
-       * the host gates the pipe launch on plan shapes where the jbuf path
-       * applies, so this stays cold): plain binary-search seeks, minimal
-       * register footprint. */
+      /* cold: series too wide for the 31-bit dt path, and the correctness
+       * fallback (per-series window not a step multiple — the host gates
+       * the pipe launch on plan shapes where the jbuf path applies).  Two
+       * probes per point, i64 dt and true division. */
       for (int g = lane; g < p.n_grid; g += WAVE) {
         int64_t t_end = p.start + (int64_t)g * p.step;
         int64_t t_start = t_end - sw.window;
-        int i = vm_upper_bound<2>(lts, count, t_start);
-        int j = vm_upper_bound<2>(lts, count, t_end);
-        emit(g, eval_rate_fused<2>(p, sw, lts, lvs, count, i, j, t_start));
+        int gi = (int)((double)(t_start - ts0) * idx_per_ms) + 1;
+        int gj = (int)((double)(t_end - ts0) * idx_per_ms) + 1;
+        int i = vm_ub_pipe(lts, count, t_start, gi);
+        int j = vm_ub_pipe(lts, count, t_end, gj);
+        emit(g, eval_rate_pipe(p, sw, lts, lvs, count, false, i, j, t_start));
       }
     }
     /* samplesScanned: every grid point of this series contributes exactly
      * samplesScannedPerCall (= 2 for rate/deriv_fast) */
-    if (lane == 0) scanned += 2ull * (unsigned long long)p.n_grid;
+    scanned += 2ull * (unsigned long long)p.n_grid;
     wave_ds_sync();
     ws = ws_n;
     s = s_n;
@@ -1825,7 +2119,6 @@ void rollup_pipe_kernel(KPlan p, KIO io) {
     n = n_n;
     si_raw = si_raw_n;
   }
-  for (int d = 32; d > 0; d >>= 1) scanned += __shfl_down((unsigned long long)scanned, d);
   if (lane == 0 && scanned) atomicAdd(io.samples_scanned, (unsigned long long)scanned);
 }
 
@@ -3465,7 +3758,10 @@ int vmgpu_rollup_exec(const vmgpu_plan* plan, uint64_t handle,
   p.jbuf_elems = 0;
   p.jbuf_mode = 0;
   if ((plan->func == VMF_RATE || plan->func == VMF_DERIV_FAST) && n_grid > 1) {
-    size_t base = (size_t)WAVES_PER_BLOCK * ((size_t)p.chunk_wave * 16 + 256);
+    /* per-wave slab incl. the pipe kernel's sentinel records when that
+     * kernel is the candidate (it stays the candidate only if a jbuf fits) */
+    size_t base = (size_t)WAVES_PER_BLOCK *
+                  vm_wave_slab_bytes(p.chunk_wave, use_pipe);
     int64_t dgp = (plan->window > 0 && plan->step > 0 &&
                    plan->window % plan->step == 0)
                       ? plan->window / plan->step : 0;
@@ -3535,7 +3831,7 @@ int vmgpu_rollup_exec(const vmgpu_plan* plan, uint64_t handle,
     uint32_t blocks = std::min<uint32_t>((b.n_wave + WAVES_PER_BLOCK - 1) / WAVES_PER_BLOCK,
                                          MAX_WAVE_BLOCKS);
     size_t lds = (size_t)WAVES_PER_BLOCK *
-                 ((size_t)p.chunk_wave * 16 + 256 +
+                 (vm_wave_slab_bytes(p.chunk_wave, use_pipe) +
                   vm_jbuf_bytes(p.jbuf_mode, p.jbuf_elems));
     /* software-pipelined register-staged variant for short series (the
      * config-2 flagship shape); VMGPU_DISABLE_PIPE=1 A/Bs the wave kernel */
