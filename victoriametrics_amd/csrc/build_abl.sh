@@ -22,7 +22,6 @@ build_one pipe_mw8 -DVMGPU_PIPE_MINWAVES=8 &
 build_one pipe_mw5 -DVMGPU_PIPE_MINWAVES=5 &
 build_one pipe_mw6 -DVMGPU_PIPE_MINWAVES=6 &
 build_one pipe_u2 -DVMGPU_PIPE_UNROLL=2 &
-build_one pipe_scat -DVMGPU_PIPE_SCATTER &
 wait
 # instruction-count cuts, one off at a time (all four are on by default),
 # and all four off (the kernel before them, plus the ungated scalar

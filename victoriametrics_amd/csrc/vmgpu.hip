@@ -56,7 +56,7 @@
  * results for series that hold an ordinary (non-stale) NaN sample, in every
  * kernel that shares the code: eval_rate_fused treats a NaN previous sample
  * as "no previous value" (rollupDerivFast tests isnan(prevValue)), and the
- * four removeCounterResets scans treat a NaN element as a clamp boundary
+ * removeCounterResets rounds treat a NaN element as a clamp boundary
  * (`values[i] < values[i-1]` is false on either side of a NaN, where the
  * fmax prefix-max used to overwrite the NaN with its predecessor).  The
  * -D...=0 builds therefore differ from the kernel before this work by
@@ -429,19 +429,119 @@ static __device__ int load_compact_wave(const int64_t* g_ts, const double* g_val
   return count;
 }
 
-/* --- fused phase A+B: staging + removeCounterResets in one pass ------ */
-/* When no sample is dropped (no stale NaNs — the overwhelmingly common
- * case), the counter-reset scan can run on the staging registers, saving
- * the whole LDS re-read pass.  Returns the kept count on success, or -1 to
- * signal "drops present, redo via load_compact_wave + rcr_scan_wave"
- * (wave-uniform).  Scan semantics identical to rcr_scan_wave below. */
+/* --- phase B: removeCounterResets as a wave scan ---------------------- */
+/* EXACT restatement of rollup.go:921-958; see file header.  The two scans
+ * that hold one sample per lane, load_rcr_fused_wave and rcr_scan_wave,
+ * share rcr_round_single: they only fetch, call the round and store.  The
+ * round hands the lane's final value to the caller's `store(x, fast)` on
+ * each of its two paths (fast = the round took the fast path: x = v + corr
+ * with corr unchanged).
+ * The two scans that hold two samples per lane, rcr_scan_pairs and
+ * rcr_scan_col_pairs further down, each keep their own copy of the pair
+ * round: every shared form of it that was built (values returned, values
+ * handed to a callable, values stored by the round) made the flagship pipe
+ * kernel 5 % slower, profiles/rcr_scan_unify.md.  A change to the scan rule
+ * is made here and in those two. */
+
+/* what a scan threads from one round to the next (all wave-uniform) */
+struct RcrCarry {
+  double corr = 0.0;      /* running correction */
+  double prev_raw = 0.0;  /* raw value of the previous round's last sample */
+  int64_t prev_ts = 0;    /* its timestamp */
+  double prev_fin = 0.0;  /* its clamped output */
+};
+
+/* Single round: lane l holds sample l of a 64-sample round.  `first_round`
+ * (wave-uniform) says that lane 0 holds element 0 of the series, `last` is
+ * the lane of the round's last active sample.  Calls store(x, fast) with
+ * the lane's final value and advances the carry. */
+template <class Store>
+static VM_DEV void rcr_round_single(double v, int64_t t, bool active,
+                                    bool first_round, int last, int64_t msi,
+                                    int lane, RcrCarry& cy, Store store) {
+  double pv = __shfl_up(v, 1);
+  int64_t pt = __shfl_up(t, 1);
+  if (lane == 0) { pv = cy.prev_raw; pt = cy.prev_ts; }
+  bool isfirst = first_round && lane == 0;
+  double d = v - pv;
+  double inc = 0.0;
+  if (!isfirst && d < 0) inc = ((-d * 8) < pv) ? (pv - v) : pv;
+  bool gap = (!isfirst && msi > 0 && (t - pt) > msi);
+  /* corrections in exact sequential order: only reset/gap events change the
+   * running correction, and f64 `c + 0.0` is an identity, so walking the
+   * (rare) event lanes reproduces the serial left-to-right sum bitwise. */
+  uint64_t em = __ballot(active && (gap || inc != 0.0));
+  /* fast path: no events, no negative deltas, and the chunk starts at or
+   * above the carried clamp level -> corrections are uniform and the
+   * monotonic clamp is a no-op. */
+  uint64_t dm = __ballot(active && !isfirst && d < 0);
+  if (em == 0 && dm == 0 &&
+      (first_round || __shfl(v, 0) + cy.corr >= cy.prev_fin)) {
+    store(v + cy.corr, true);
+    cy.prev_raw = __shfl(v, last);
+    cy.prev_ts = __shfl(t, last);
+    cy.prev_fin = cy.prev_raw + cy.corr;
+    return;
+  }
+  double c = cy.corr;
+  double mycorr = cy.corr;
+  while (em) {
+    int b = __ffsll((unsigned long long)em) - 1;
+    em &= em - 1;
+    double ib = __shfl(inc, b);
+    int gb = __shfl((int)gap, b);
+    double cn = gb ? 0.0 : (c + ib);
+    if (lane >= b) mycorr = cn;
+    c = cn;
+  }
+  double fin = v + mycorr;
+  /* monotonic clamp (rollup.go:952-956) = segmented prefix max; a gap
+   * element keeps its raw value and is exempt (the Go `continue`).  A NaN
+   * element keeps its value and restarts the running max, as the
+   * reference's `values[i] < values[i-1]` test does on either side of it. */
+  bool bnd = isfirst || gap || vm_isnan(fin);
+  double x = fin;
+#if VMGPU_PIPE_SKIP_PMAX
+  /* clamp shortcut (vm_clamp_violates): one neighbour shuffle + ballot;
+   * lanes past the series end sit above every active one and feed nothing
+   * that is stored or carried, so they are left out */
+  double pfin = __shfl_up(fin, 1);
+  if (lane == 0) pfin = cy.prev_fin;
+  const bool clamp_needed =
+      __ballot(active && !bnd && vm_clamp_violates(fin, pfin)) != 0;
+#else
+  const bool clamp_needed = true;
+#endif
+  if (clamp_needed) {
+    int f = bnd ? 1 : 0;
+    if (lane == 0 && !bnd) x = fmax(x, cy.prev_fin);
+    for (int dlt = 1; dlt < WAVE; dlt <<= 1) {
+      double xo = __shfl_up(x, dlt);
+      int fo = __shfl_up(f, dlt);
+      if (lane >= dlt) {
+        if (!f) x = fmax(x, xo);
+        f = f | fo;
+      }
+    }
+  }
+  /* store() comes before the carry update: an in-place caller's store reads
+   * cy.corr, and must see the correction the round started with */
+  store(x, false);
+  cy.corr = c;
+  cy.prev_raw = __shfl(v, last);
+  cy.prev_ts = __shfl(t, last);
+  cy.prev_fin = __shfl(x, last);
+}
+
+/* Fused staging + scan of the wave kernel: when no sample is dropped (no
+ * stale NaNs — the overwhelmingly common case), the scan runs on the
+ * staging registers, saving the whole LDS re-read pass.  Returns the kept
+ * count on success, or -1 to signal "drops present, redo via
+ * load_compact_wave + rcr_scan_wave" (wave-uniform). */
 static __device__ int load_rcr_fused_wave(const int64_t* g_ts, const double* g_vals,
                                           int64_t n, int64_t* d_ts, double* d_vals,
                                           bool drop_stale, int64_t msi, int lane) {
-  double corr = 0.0;
-  double prev_raw = 0.0;
-  int64_t prev_ts = 0;
-  double prev_fin = 0.0;
+  RcrCarry cy;
   for (int64_t base = 0; base < n; base += WAVE) {
     int64_t k = base + lane;
     bool active = k < n;
@@ -453,149 +553,35 @@ static __device__ int load_rcr_fused_wave(const int64_t* g_ts, const double* g_v
     }
     if (drop_stale && __ballot(active && vm_is_stale_nan(v)) != 0) return -1;
     if (active) d_ts[k] = t;
-    /* scan round (identical to rcr_scan_wave, values from registers) */
-    double pv = __shfl_up(v, 1);
-    int64_t pt = __shfl_up(t, 1);
-    if (lane == 0) { pv = prev_raw; pt = prev_ts; }
-    bool isfirst = (k == 0);
-    double d = v - pv;
-    double inc = 0.0;
-    if (!isfirst && d < 0) inc = ((-d * 8) < pv) ? (pv - v) : pv;
-    bool gap = (!isfirst && msi > 0 && (t - pt) > msi);
-    uint64_t em = __ballot(active && (gap || inc != 0.0));
-    uint64_t dm = __ballot(active && !isfirst && d < 0);
     int last = (int)(n - base - 1);
     if (last > 63) last = 63;
-    if (em == 0 && dm == 0 &&
-        (base == 0 || __shfl(v, 0) + corr >= prev_fin)) {
-      if (active) d_vals[k] = v + corr;
-      prev_raw = __shfl(v, last);
-      prev_ts = __shfl(t, last);
-      prev_fin = prev_raw + corr;
-      continue;
-    }
-    double c = corr;
-    double mycorr = corr;
-    while (em) {
-      int b = __ffsll((unsigned long long)em) - 1;
-      em &= em - 1;
-      double ib = __shfl(inc, b);
-      int gb = __shfl((int)gap, b);
-      double cn = gb ? 0.0 : (c + ib);
-      if (lane >= b) mycorr = cn;
-      c = cn;
-    }
-    double fin = v + mycorr;
-    /* a NaN element keeps its value and restarts the running max, as the
-     * reference's `values[i] < values[i-1]` test does on either side of it */
-    bool bnd = isfirst || gap || vm_isnan(fin);
-    double x = fin;
-    int f = bnd ? 1 : 0;
-    if (lane == 0 && !bnd) x = fmax(x, prev_fin);
-    for (int dlt = 1; dlt < WAVE; dlt <<= 1) {
-      double xo = __shfl_up(x, dlt);
-      int fo = __shfl_up(f, dlt);
-      if (lane >= dlt) {
-        if (!f) x = fmax(x, xo);
-        f = f | fo;
-      }
-    }
-    if (active) d_vals[k] = x;
-    corr = c;
-    prev_raw = __shfl(v, last);
-    prev_ts = __shfl(t, last);
-    prev_fin = __shfl(x, last);
+    rcr_round_single(v, t, active, base == 0, last, msi, lane, cy,
+                     [&](double x, bool) {
+                       if (active) d_vals[k] = x;
+                     });
   }
   return (int)n;
 }
 
-/* --- phase B: removeCounterResets over the dense column -------------- */
-/* EXACT restatement of rollup.go:921-958 as a wave scan; see file header. */
+/* In-place scan over a dense column (stride STR in int64 units): the wave
+ * and pipe kernels' fallback behind load_compact_wave. */
 template <int STR = 1>
 static __device__ void rcr_scan_wave(int64_t* d_ts, double* d_vals, int count,
                                      int64_t msi, int lane) {
-  double corr = 0.0;       /* running correction */
-  double prev_raw = 0.0;   /* raw value of previous element */
-  int64_t prev_ts = 0;
-  double prev_fin = 0.0;   /* clamped output of previous element */
+  RcrCarry cy;
   for (int base = 0; base < count; base += WAVE) {
     int k = base + lane;
     bool active = k < count;
     double v = active ? d_vals[k * STR] : 0.0;
     int64_t t = active ? d_ts[k * STR] : 0;
-    double pv = __shfl_up(v, 1);
-    int64_t pt = __shfl_up(t, 1);
-    if (lane == 0) { pv = prev_raw; pt = prev_ts; }
-    bool isfirst = (k == 0);
-    double d = v - pv;
-    double inc = 0.0;
-    if (!isfirst && d < 0) inc = ((-d * 8) < pv) ? (pv - v) : pv;
-    bool gap = (!isfirst && msi > 0 && (t - pt) > msi);
-    /* corrections in exact sequential order: only reset/gap events change the
-     * running correction, and f64 `c + 0.0` is an identity, so walking the
-     * (rare) event lanes reproduces the serial left-to-right sum bitwise. */
-    uint64_t em = __ballot(active && (gap || inc != 0.0));
-    /* fast path: no events, no negative deltas, and the chunk starts at or
-     * above the carried clamp level -> corrections are uniform and the
-     * monotonic clamp is a no-op. */
-    uint64_t dm = __ballot(active && !isfirst && d < 0);
-    int last_fast = count - base - 1;
-    if (last_fast > 63) last_fast = 63;
-    if (em == 0 && dm == 0 &&
-        (base == 0 || __shfl(v, 0) + corr >= prev_fin)) {
-      if (corr != 0.0 && active) d_vals[k * STR] = v + corr;
-      prev_raw = __shfl(v, last_fast);
-      prev_ts = __shfl(t, last_fast);
-      prev_fin = prev_raw + corr;
-      continue;
-    }
-    double c = corr;
-    double mycorr = corr;
-    while (em) {
-      int b = __ffsll((unsigned long long)em) - 1;
-      em &= em - 1;
-      double ib = __shfl(inc, b);
-      int gb = __shfl((int)gap, b);
-      double cn = gb ? 0.0 : (c + ib);
-      if (lane >= b) mycorr = cn;
-      c = cn;
-    }
-    double fin = v + mycorr;
-    /* monotonic clamp (rollup.go:952-956) = segmented prefix max; a gap
-     * element keeps its raw value and is exempt (the Go `continue`). */
-    /* a NaN element keeps its value and restarts the running max, as the
-     * reference's `values[i] < values[i-1]` test does on either side of it */
-    bool bnd = isfirst || gap || vm_isnan(fin);
-    double x = fin;
-#if VMGPU_PIPE_SKIP_PMAX
-    /* clamp shortcut (vm_clamp_violates); lanes past the series end feed
-     * nothing that is stored or carried */
-    double pfin = __shfl_up(fin, 1);
-    if (lane == 0) pfin = prev_fin;
-    const bool clamp_needed =
-        __ballot(active && !bnd && vm_clamp_violates(fin, pfin)) != 0;
-#else
-    const bool clamp_needed = true;
-#endif
-    if (clamp_needed) {
-      int f = bnd ? 1 : 0;
-      if (lane == 0 && !bnd) x = fmax(x, prev_fin);
-      for (int dlt = 1; dlt < WAVE; dlt <<= 1) {
-        double xo = __shfl_up(x, dlt);
-        int fo = __shfl_up(f, dlt);
-        if (lane >= dlt) {
-          if (!f) x = fmax(x, xo);
-          f = f | fo;
-        }
-      }
-    }
-    if (active) d_vals[k * STR] = x;
     int last = count - base - 1;
     if (last > 63) last = 63;
-    corr = c;
-    prev_raw = __shfl(v, last);
-    prev_ts = __shfl(t, last);
-    prev_fin = __shfl(x, last);
+    /* a fast round with no correction leaves the column as it is */
+    rcr_round_single(v, t, active, base == 0, last, msi, lane, cy,
+                     [&](double x, bool fast) {
+                       if (fast && cy.corr == 0.0) return;
+                       if (active) d_vals[k * STR] = x;
+                     });
   }
 }
 
@@ -839,20 +825,16 @@ static VM_DEV void vm_emit_value(const KPlan& p, const KIO& io, uint32_t s,
   }
 }
 
-/* Fused branch-free rate/deriv_fast evaluator (rollupDerivFast,
- * rollup.go:1954-1989 + the rfa construction of doInternal:779-810 reduced
- * to the fields rate reads): six independent LDS loads + selects. */
-#ifndef VMGPU_PIPE_NO_TV
-#define VMGPU_PIPE_NO_TV 0
-#endif
-
 /* 16-byte (t, v) record of the pair-interleaved LDS slab */
 struct __align__(16) vm_tv {
   int64_t t;
   double v;
 };
 
-/* SENT: ts/vals point into the pipe kernel's sentinel-padded slab and
+/* Fused branch-free rate/deriv_fast evaluator (rollupDerivFast,
+ * rollup.go:1954-1989 + the rfa construction of doInternal:779-810 reduced
+ * to the fields rate reads): six independent LDS loads + selects.
+ * SENT: ts/vals point into the pipe kernel's sentinel-padded slab and
  * 0 <= i <= j <= count, so the three record indices i-1, i, j-1 lie in
  * [-1, count] and need no clamp.  Whenever one of them lands on a sentinel
  * record the selects below already discard what was read there:
@@ -884,7 +866,7 @@ static VM_DEV double eval_rate_fused(const KPlan& p, const SeriesWindow& sw,
   }
   double v_prevc, v_first, v_end;
   int64_t t_prevc, t_first, t_end_s;
-  if constexpr (STR == 2 && !VMGPU_PIPE_NO_TV) {
+  if constexpr (STR == 2) {
     /* one b128 LDS read per boundary role instead of two scattered b64s */
     const vm_tv* tv = (const vm_tv*)ts;
     vm_tv a = tv[im1], b = tv[ii], c = tv[jm1];
@@ -993,7 +975,7 @@ static VM_DEV uint64_t eval_grid_point(const KPlan& p, const SeriesWindow& sw,
 /* kernel 1: one wave per series (n <= CHUNK_WAVE)                    */
 /* ------------------------------------------------------------------ */
 
-template <int FUNC_CT, bool GACC = false, bool PREF = false>
+template <int FUNC_CT, bool PREF = false>
 __global__ __launch_bounds__(BLOCK_THREADS) void rollup_wave_kernel(KPlan p, KIO io) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int wave_in_block = threadIdx.x / WAVE;
@@ -1014,102 +996,27 @@ __global__ __launch_bounds__(BLOCK_THREADS) void rollup_wave_kernel(KPlan p, KIO
   const uint32_t wave_id = blockIdx.x * WAVES_PER_BLOCK + wave_in_block;
   const uint32_t wave_stride = gridDim.x * WAVES_PER_BLOCK;
 
-  /* GACC (compile-time variant, launched only for grouped rate plans with
-   * n_grid <= 4*WAVE on a group-relayouted batch): per-point results
-   * accumulate in registers across each group's contiguous series run and
-   * flush with ONE atomic per (group, point).  Commutativity makes partial
-   * runs safe: flushing is only needed on group change and at kernel end. */
-  double accv[GACC ? 4 : 1], accc[GACC ? 4 : 1];
-  int cur_grp = -1;
-  double acc_init = 0.0;
-  if constexpr (GACC) {
-    acc_init = (p.aggr == VMGPU_AGGR_MIN) ? vm_dinf()
-               : (p.aggr == VMGPU_AGGR_MAX) ? -vm_dinf()
-               : (p.aggr == VMGPU_AGGR_GEOMEAN) ? 1.0 : 0.0;
-#pragma unroll
-    for (int u = 0; u < 4; u++) { accv[u] = acc_init; accc[u] = 0.0; }
-  }
-  auto acc_flush = [&]() {
-    if constexpr (GACC) {
-      if (cur_grp < 0) return;
-#pragma unroll
-      for (int u = 0; u < 4; u++) {
-        int g = u * WAVE + lane;
-        if (g < p.n_grid && accc[u] > 0.0) {
-          double* gv = io.out + (size_t)cur_grp * (size_t)p.n_grid + (size_t)g;
-          double* gc = io.out_counts + (size_t)cur_grp * (size_t)p.n_grid + (size_t)g;
-          switch (p.aggr) {
-            case VMGPU_AGGR_SUM:  atomicAdd(gv, accv[u]); *gc = 1.0; break;
-            case VMGPU_AGGR_AVG:  atomicAdd(gv, accv[u]); atomicAdd(gc, accc[u]); break;
-            case VMGPU_AGGR_MIN:  vm_atomic_min_f64(gv, accv[u]); *gc = 1.0; break;
-            case VMGPU_AGGR_MAX:  vm_atomic_max_f64(gv, accv[u]); *gc = 1.0; break;
-            case VMGPU_AGGR_COUNT:
-            case VMGPU_AGGR_GROUP: atomicAdd(gv, accc[u]); *gc = 1.0; break;
-            case VMGPU_AGGR_SUM2: atomicAdd(gv, accv[u]); *gc = 1.0; break;
-            case VMGPU_AGGR_GEOMEAN:
-              vm_atomic_mul_f64(gv, accv[u]); atomicAdd(gc, accc[u]); break;
-            default: break;
-          }
-        }
-        accv[u] = acc_init;
-        accc[u] = 0.0;
-      }
-      cur_grp = -1;
-    }
-  };
-
-  /* GACC: contiguous spans keep the group-relayouted runs within one wave;
-   * otherwise strided (XCD-spread) assignment as before */
-  uint32_t ws_begin, ws_end, ws_step;
-  if constexpr (GACC) {
-    uint32_t span = (io.n_sel + wave_stride - 1) / wave_stride;
-    ws_begin = wave_id * span;
-    ws_end = ws_begin + span;
-    if (ws_end > io.n_sel) ws_end = io.n_sel;
-    if (ws_begin > io.n_sel) ws_begin = io.n_sel;
-    ws_step = 1;
-  } else {
-    ws_begin = wave_id;
-    ws_end = io.n_sel;
-    ws_step = wave_stride;
-  }
-  for (uint32_t ws = ws_begin; ws < ws_end; ws += ws_step) {
+  /* strided (XCD-spread) series assignment */
+  for (uint32_t ws = wave_id; ws < io.n_sel; ws += wave_stride) {
     uint32_t s = io.series_sel ? io.series_sel[ws] : ws;
     uint64_t lo = io.offsets[s];
     int64_t n = (int64_t)(io.offsets[s + 1] - lo);
 
-#ifdef VMGPU_ABL_RAW_COPY
-    int count = (int)n;
-    for (int64_t k = lane; k < n; k += WAVE) {
-      lts[k] = io.ts[lo + k];
-      lvs[k] = io.vals[lo + k];
-    }
-    wave_lds_sync();
-#ifndef VMGPU_ABL_NO_RCR
-    if (p.rcr) rcr_scan_wave(lts, lvs, count, p.max_staleness, lane);
-    wave_lds_sync();
-#endif
-#else
     int count = -1;
-#ifndef VMGPU_ABL_NO_RCR
     if (p.rcr)
       count = load_rcr_fused_wave(io.ts + lo, io.vals + lo, n, lts, lvs,
                                   p.drop_stale != 0, p.max_staleness, lane);
-#endif
     if (count < 0) {
       /* no rcr, or stale NaNs present: compact first, then scan */
       count = load_compact_wave(io.ts + lo, io.vals + lo, n, lts, lvs,
                                 p.drop_stale != 0, lane);
       wave_lds_sync();
-#ifndef VMGPU_ABL_NO_RCR
       if (p.rcr) rcr_scan_wave(lts, lvs, count, p.max_staleness, lane);
-#endif
     }
     wave_lds_sync();
-#endif
     /* compile-time gated: the inlined preFunc body costs ~10% on the hot
      * rate path when merely PRESENT (VGPR 32 -> 44), so it lives in its
-     * own instantiation like GACC */
+     * own instantiation */
     if constexpr (PREF) {
       if (p.pre_func) pre_func_wave(lts, lvs, count, p.pre_func, lane);
     }
@@ -1138,7 +1045,6 @@ __global__ __launch_bounds__(BLOCK_THREADS) void rollup_wave_kernel(KPlan p, KIO
       int64_t span_ms = lts[count - 1] - ts0;
       idx_per_ms = span_ms > 0 ? (double)(count - 1) / (double)span_ms : 0.0;
     }
-#if !defined(VMGPU_ABL_NO_SEEK) && !defined(VMGPU_ABL_NO_EVAL)
     if constexpr (FUNC_CT == VMF_RATE || FUNC_CT == VMF_DERIV_FAST) {
       /* Both fast paths exploit i(g) = j(g-dg) when the window is a step
        * multiple (the standard rate(m[5m]) @ 15s grid): the window START
@@ -1207,15 +1113,6 @@ __global__ __launch_bounds__(BLOCK_THREADS) void rollup_wave_kernel(KPlan p, KIO
       if (p.jbuf_mode >= 1 &&
           (size_t)p.n_grid * 2 <= vm_jbuf_bytes(p.jbuf_mode, p.jbuf_elems) &&
           dg64 > 0 && count <= 65535) {
-        bool use_acc = false;
-        if constexpr (GACC) {
-          int sgrp = io.group_ids ? io.group_ids[s] : -1;
-          use_acc = (sgrp >= 0);
-          if (use_acc && sgrp != cur_grp) {
-            acc_flush();
-            cur_grp = sgrp;
-          }
-        }
         for (int g = lane; g < p.n_grid; g += WAVE) {
           int64_t t_end = p.start + (int64_t)g * p.step;
           int gj = (int)((double)(t_end - ts0) * idx_per_ms) + 1;
@@ -1237,27 +1134,8 @@ __global__ __launch_bounds__(BLOCK_THREADS) void rollup_wave_kernel(KPlan p, KIO
                 int gi = (int)((double)(t_start - ts0) * idx_per_ms) + 1;
                 i = vm_ub_hint_fast(lts, count, t_start, gi);
               }
-              double v = eval_rate_fused(p, sw, lts, lvs, count, i, j, t_start);
-              if (GACC && use_acc) {
-                if constexpr (GACC) {
-                  if (!vm_isnan(v)) {
-                    switch (p.aggr) {
-                      case VMGPU_AGGR_SUM:
-                      case VMGPU_AGGR_AVG:  accv[u] += v; break;
-                      case VMGPU_AGGR_MIN:
-                        accv[u] = (v < accv[u]) ? v : accv[u]; break;
-                      case VMGPU_AGGR_MAX:
-                        accv[u] = (v > accv[u]) ? v : accv[u]; break;
-                      case VMGPU_AGGR_SUM2: accv[u] += v * v; break;
-                      case VMGPU_AGGR_GEOMEAN: accv[u] *= v; break;
-                      default: break; /* COUNT/GROUP count only */
-                    }
-                    accc[u] += 1.0;
-                  }
-                }
-              } else {
-                vm_emit_value(p, io, s, g, v);
-              }
+              vm_emit_value(p, io, s, g,
+                            eval_rate_fused(p, sw, lts, lvs, count, i, j, t_start));
               scanned += 2;
             }
           }
@@ -1266,7 +1144,6 @@ __global__ __launch_bounds__(BLOCK_THREADS) void rollup_wave_kernel(KPlan p, KIO
         continue;
       }
     }
-#endif
     for (int g0 = 0; g0 < p.n_grid; g0 += 4 * WAVE) {
       /* four grid points per lane per outer iteration: independent seek and
        * eval chains that the scheduler interleaves (the phases are LDS-
@@ -1279,11 +1156,6 @@ __global__ __launch_bounds__(BLOCK_THREADS) void rollup_wave_kernel(KPlan p, KIO
           int64_t t_start = t_end - sw.window;
           int gi = (int)((double)(t_start - ts0) * idx_per_ms) + 1;
           int gj = (int)((double)(t_end - ts0) * idx_per_ms) + 1;
-#ifdef VMGPU_ABL_NO_SEEK
-          int i = gi < 0 ? 0 : (gi > count ? count : gi);
-          int j = gj < 0 ? 0 : (gj > count ? count : gj);
-          if (j < i) j = i;
-#else
           int i, j;
           if constexpr (FUNC_CT == VMF_RATE || FUNC_CT == VMF_DERIV_FAST) {
             i = vm_ub_hint_fast(lts, count, t_start, gi);
@@ -1292,11 +1164,6 @@ __global__ __launch_bounds__(BLOCK_THREADS) void rollup_wave_kernel(KPlan p, KIO
             i = vm_ub_hint(lts, count, t_start, gi);
             j = vm_ub_hint(lts, count, t_end, gj);
           }
-#endif
-#ifdef VMGPU_ABL_NO_EVAL
-          io.out[(size_t)s * (size_t)p.n_grid + (size_t)g] = (j > 0 && j <= count) ? lvs[j - 1] : 0.0;
-          scanned += 2;
-#else
           if constexpr (FUNC_CT == VMF_RATE || FUNC_CT == VMF_DERIV_FAST) {
             vm_emit_value(p, io, s, g,
                           eval_rate_fused(p, sw, lts, lvs, count, i, j, t_start));
@@ -1304,13 +1171,11 @@ __global__ __launch_bounds__(BLOCK_THREADS) void rollup_wave_kernel(KPlan p, KIO
           } else {
             scanned += eval_grid_point_ij<FUNC_CT>(p, sw, lts, lvs, count, g, s, io, i, j);
           }
-#endif
         }
       }
     }
     wave_lds_sync();
   }
-  acc_flush();
   /* reduce samplesScanned: wave shuffle + one atomic per wave */
   for (int d = 32; d > 0; d >>= 1) scanned += __shfl_down((unsigned long long)scanned, d);
   if (lane == 0 && scanned) atomicAdd(io.samples_scanned, (unsigned long long)scanned);
@@ -1323,10 +1188,13 @@ __global__ __launch_bounds__(BLOCK_THREADS) void rollup_wave_kernel(KPlan p, KIO
 /* bound (profiles/round1_final.md §5: FETCH/WRITE ≈ algorithmic but  */
 /* ACTIVE_INST_ANY ≈ 30% at 7 waves/SIMD).  This variant restructures */
 /* the per-series phases so the memory system never drains:           */
-/*   - the series' columns are loaded straight into REGISTERS (up to  */
-/*     PIPE_CHUNKS coalesced b64 loads per column in flight at once), */
+/*   - the series' columns are loaded straight into REGISTERS as      */
+/*     pairs: lane l holds samples (2l, 2l+1) of each 128-sample      */
+/*     chunk, one b128 load per column per chunk, PIPE_PCHUNKS chunks */
+/*     in flight at once,                                             */
 /*   - the removeCounterResets scan consumes those registers while    */
-/*     writing the corrected columns to LDS (no LDS re-read pass),    */
+/*     writing the corrected pair-interleaved slab to LDS (no LDS     */
+/*     re-read pass),                                                 */
 /*   - the NEXT series' loads are issued as soon as the registers die,*/
 /*     overlapping scrape/seek/eval/emit of the current series,       */
 /*   - every phase barrier is lgkm-only (wave_ds_sync), so the        */
@@ -1335,7 +1203,7 @@ __global__ __launch_bounds__(BLOCK_THREADS) void rollup_wave_kernel(KPlan p, KIO
 /* j-cache seeks, same evaluators.                                    */
 /* ------------------------------------------------------------------ */
 
-#define PIPE_CHUNKS 4 /* series cap = PIPE_CHUNKS*WAVE = 256 samples */
+#define PIPE_PCHUNKS 2 /* pair chunks: 2 x 128 samples = 256 cap */
 
 /* Pair-rounds removeCounterResets over an LDS/global COLUMN (stride STR
  * in int64 units): the rcr_scan_pairs logic with per-round pair loads
@@ -1460,8 +1328,6 @@ static __device__ void rcr_scan_col_pairs(int64_t* d_ts, double* d_vals,
     }
   }
 }
-
-#define PIPE_PCHUNKS 2 /* pair chunks: 2 x 128 samples = 256 cap */
 
 /* Pair-register removeCounterResets: lane l holds samples (2l, 2l+1) of
  * each 128-sample chunk (ONE b128 global load per column per chunk).
@@ -1668,26 +1534,6 @@ void rollup_pipe_kernel(KPlan p, KIO io) {
   int64_t rt0[PIPE_PCHUNKS], rt1[PIPE_PCHUNKS];
   double rv0[PIPE_PCHUNKS], rv1[PIPE_PCHUNKS];
 
-  /* J-scatter mode (A/B builds only: -DVMGPU_PIPE_SCATTER): plan-uniform
-   * window that is a step multiple + an ext jbuf (jbuf_mode 2).  The
-   * staging scan then builds the full upper-bound map J[g+sdg] =
-   * #samples <= t_end(g) and the eval phase does no seeks at all.
-   * Measured SLOWER than the probe j-cache at config 2 (the divergent
-   * range writes sit on the serial scan chain) — compiled out so the
-   * default kernel does not pay its register pressure. */
-#ifdef VMGPU_PIPE_SCATTER
-  int scat_dg = 0;
-  if (p.jbuf_mode == 2 && p.window > 0 && p.step > 0 &&
-      p.window % p.step == 0) {
-    int64_t d = p.window / p.step;
-    if (d > 0 && p.n_grid + d <= p.jbuf_elems) scat_dg = (int)d;
-  }
-  const double inv_gstep = 1.0 / (double)p.step;
-#else
-  const int scat_dg = 0;
-  const double inv_gstep = 0.0;
-#endif
-
   /* wave_id is wave-uniform by construction; readfirstlane makes that
    * provable, so the per-series descriptor reads below become scalar
    * (s_load, lgkm-counted) instead of divergent vector loads, and the
@@ -1712,17 +1558,8 @@ void rollup_pipe_kernel(KPlan p, KIO io) {
       for (int c = 0; c < PIPE_PCHUNKS; c++) {
         int64_t k = (int64_t)c * 2 * WAVE + 2 * lane;
         if (k > nm2) k = nm2; /* batch columns carry 16 B slack for this */
-#ifdef VMGPU_PIPE_NT
-        typedef long long v2i64 __attribute__((ext_vector_type(2)));
-        typedef double v2f64 __attribute__((ext_vector_type(2)));
-        v2i64 tpv = __builtin_nontemporal_load((const v2i64*)(gts + k));
-        v2f64 vpv = __builtin_nontemporal_load((const v2f64*)(gvs + k));
-        vm_i64x2 tp = {tpv.x, tpv.y};
-        double2 vp = {vpv.x, vpv.y};
-#else
         vm_i64x2 tp = *(const vm_i64x2*)(gts + k);
         double2 vp = *(const double2*)(gvs + k);
-#endif
         rt0[c] = tp.x;
         rt1[c] = tp.y;
         rv0[c] = vp.x;
@@ -1743,13 +1580,6 @@ void rollup_pipe_kernel(KPlan p, KIO io) {
       lo_n = io.offsets[s_n];
       n_n = (int64_t)(io.offsets[s_n + 1] - lo_n);
       if (io.series_si) si_raw_n = io.series_si[s_n];
-    }
-    /* J-scatter init: zero = "no sample <= t_end" for positions before the
-     * first sample's range (upper bound 0) */
-    if (scat_dg > 0) {
-      const int ext = p.n_grid + scat_dg;
-      for (int e = lane; e < ext; e += WAVE) jbuf[e] = 0;
-      wave_ds_sync();
     }
     /* stage the current series into LDS from registers (rcr fused);
      * odd-offset series (no 16-B-aligned pair loads) fall to the global
@@ -1797,17 +1627,8 @@ void rollup_pipe_kernel(KPlan p, KIO io) {
       for (int c = 0; c < PIPE_PCHUNKS; c++) {
         int64_t k = (int64_t)c * 2 * WAVE + 2 * lane;
         if (k > nm2) k = nm2;
-#ifdef VMGPU_PIPE_NT
-        typedef long long v2i64 __attribute__((ext_vector_type(2)));
-        typedef double v2f64 __attribute__((ext_vector_type(2)));
-        v2i64 tpv = __builtin_nontemporal_load((const v2i64*)(gts + k));
-        v2f64 vpv = __builtin_nontemporal_load((const v2f64*)(gvs + k));
-        vm_i64x2 tp = {tpv.x, tpv.y};
-        double2 vp = {vpv.x, vpv.y};
-#else
         vm_i64x2 tp = *(const vm_i64x2*)(gts + k);
         double2 vp = *(const double2*)(gvs + k);
-#endif
         rt0[c] = tp.x;
         rt1[c] = tp.y;
         rv0[c] = vp.x;
@@ -1820,16 +1641,6 @@ void rollup_pipe_kernel(KPlan p, KIO io) {
                                    p.drop_stale != 0, lane);
       wave_ds_sync();
       if (p.rcr) rcr_scan_wave<2>(lts, lvs, count, p.max_staleness, lane);
-      if (scat_dg > 0) {
-        /* the register scatter saw pre-compaction indices: rebuild J by
-         * direct binary search over the compacted column */
-        wave_ds_sync();
-        const int ext = p.n_grid + scat_dg;
-        for (int e = lane; e < ext; e += WAVE) {
-          int64_t t_end = p.start + (int64_t)(e - scat_dg) * p.step;
-          jbuf[e] = (uint16_t)vm_upper_bound<2>(lts, count, t_end);
-        }
-      }
     }
 #if VMGPU_PIPE_SENTINEL
     /* back sentinels behind the now-final count (count <= chunk_wave, so
@@ -1928,11 +1739,7 @@ void rollup_pipe_kernel(KPlan p, KIO io) {
           }
         }
       } else {
-#ifdef VMGPU_PIPE_NT
-        __builtin_nontemporal_store(v, out_row + g);
-#else
         out_row[g] = v;
-#endif
       }
     };
     const int64_t t_step_wave = (int64_t)WAVE * p.step;
@@ -1940,26 +1747,9 @@ void rollup_pipe_kernel(KPlan p, KIO io) {
     if constexpr (FUNC_CT == VMF_RATE || FUNC_CT == VMF_DERIV_FAST) {
       const bool dt32 = VMGPU_PIPE_DT_FAST != 0;
       const bool dt_ok = dt32_series || !dt32;
-      if (scat_dg > 0 && dt_ok) {
-        /* scatter-J eval: J was built during staging; no seeks at all. */
-        int gs = lane;
-        int64_t te_s = p.start + (int64_t)lane * p.step;
-        for (; gs < p.n_grid; gs += WAVE, te_s += t_step_wave) {
-          int j = jbuf[gs + scat_dg];
-          int i = jbuf[gs];
-#ifdef VMGPU_PIPE_ABL_NO_EVAL
-          emit(gs, (j > 0 && j <= count) ? lvs[(j - 1) * 2] : 0.0);
-          (void)i;
-#else
-          emit(gs, eval_rate_pipe(p, sw, lts, lvs, count, dt32, i, j,
-                                      te_s - sw.window));
-#endif
-        }
-        done = true;
-      }
       int dg64 = (sw.window > 0 && p.step > 0 && sw.window % p.step == 0)
                      ? (int)(sw.window / p.step) : 0;
-      if (!done && dt_ok && p.jbuf_mode >= 1 &&
+      if (dt_ok && p.jbuf_mode >= 1 &&
           (size_t)p.n_grid * 2 <= vm_jbuf_bytes(p.jbuf_mode, p.jbuf_elems) &&
           dg64 > 0 && count <= 65535) {
         if (dg64 < WAVE) {
@@ -2023,11 +1813,7 @@ void rollup_pipe_kernel(KPlan p, KIO io) {
 #else
             int gj = (int)((double)(te - ts0) * idx_per_ms) + 1;
 #endif
-#ifdef VMGPU_PIPE_WALK_PROBE
-            jbuf[gf] = (uint16_t)vm_ub_hint<2>(lts, count, te, gj);
-#else
             jbuf[gf] = (uint16_t)vm_ub_pipe(lts, count, te, gj);
-#endif
           }
           if (gf < p.n_grid) {
 #if VMGPU_PIPE_HINT_ACC
@@ -2035,11 +1821,7 @@ void rollup_pipe_kernel(KPlan p, KIO io) {
 #else
             int gj = (int)((double)(te - ts0) * idx_per_ms) + 1;
 #endif
-#ifdef VMGPU_PIPE_WALK_PROBE
-            jbuf[gf] = (uint16_t)vm_ub_hint<2>(lts, count, te, gj);
-#else
             jbuf[gf] = (uint16_t)vm_ub_pipe(lts, count, te, gj);
-#endif
           }
         }
         wave_ds_sync();
@@ -2196,10 +1978,8 @@ __global__ __launch_bounds__(BLOCK_THREADS) void rollup_block_kernel(KPlan p, KI
         }
       }
     }
-#ifndef VMGPU_ABL_NO_RCR
     if (p.rcr && wave == 0)
       rcr_scan_col_pairs<1>(lts, lvs, count, p.max_staleness, lane);
-#endif
     __syncthreads();
     if (p.pre_func && wave == 0)
       pre_func_wave(lts, lvs, count, p.pre_func, lane);
@@ -3018,36 +2798,14 @@ template <int FUNC_CT>
 static void launch_rollup_t(int which, uint32_t blocks, size_t lds,
                             const KPlan& p, const KIO& w, hipStream_t stream) {
   if (which == 0) {
-    /* grouped rate plans with grids the accumulator covers take the
-     * register-run variant (GACC) — valid because grouped batches are
-     * physically relayouted by group at creation.  preFunc plans take the
-     * PREF instantiation (compile-time gated for the same reason). */
-    /* A/B measured (profiles/round1_final.md §4): the register-run
-     * accumulator (GACC) is 0.4 ms SLOWER than plain per-point atomics at
-     * config 3 (2.89 vs 3.30 ms) — the accumulate/flush instruction cost
-     * exceeds the scattered-atomic cost on this issue-bound kernel.  The
-     * instantiation stays compiled (VMGPU_ABL_GACC re-enables it for
-     * future A/Bs) but plain atomics are the default. */
-    bool gacc = false;
-#ifdef VMGPU_ABL_GACC
-    gacc = (FUNC_CT == VMF_RATE || FUNC_CT == VMF_DERIV_FAST) &&
-           p.aggr != VMGPU_AGGR_NONE && w.group_ids != nullptr &&
-           p.n_grid <= 4 * WAVE;
-#endif
-    if (p.pre_func != 0) {
-      if (gacc)
-        hipLaunchKernelGGL((rollup_wave_kernel<FUNC_CT, true, true>),
-                           dim3(blocks), dim3(BLOCK_THREADS), lds, stream, p, w);
-      else
-        hipLaunchKernelGGL((rollup_wave_kernel<FUNC_CT, false, true>),
-                           dim3(blocks), dim3(BLOCK_THREADS), lds, stream, p, w);
-    } else if (gacc) {
-      hipLaunchKernelGGL((rollup_wave_kernel<FUNC_CT, true, false>), dim3(blocks),
+    /* preFunc plans take the PREF instantiation (compile-time gated, see
+     * the kernel) */
+    if (p.pre_func != 0)
+      hipLaunchKernelGGL((rollup_wave_kernel<FUNC_CT, true>), dim3(blocks),
                          dim3(BLOCK_THREADS), lds, stream, p, w);
-    } else {
-      hipLaunchKernelGGL((rollup_wave_kernel<FUNC_CT, false, false>), dim3(blocks),
+    else
+      hipLaunchKernelGGL((rollup_wave_kernel<FUNC_CT, false>), dim3(blocks),
                          dim3(BLOCK_THREADS), lds, stream, p, w);
-    }
   } else if (which == 1) {
     hipLaunchKernelGGL(rollup_block_kernel<FUNC_CT>, dim3(blocks),
                        dim3(BLOCK_THREADS), lds, stream, p, w);
@@ -3737,12 +3495,13 @@ int vmgpu_rollup_exec(const vmgpu_plan* plan, uint64_t handle,
    * occupancy loss; J-only scatter: 2.77 ms from the boundary-fixup +
    * divergent write cost) vs 2.51 ms for the j-cache.  Mode 2 remains
    * selectable for grids too large for the u16 cache. */
-  /* pipe eligibility decides the jbuf flavor: the pipelined kernel builds
-   * the full ext J map during its staging scan (mode 2), everything else
-   * uses the probe-filled u16 j-cache (mode 1). */
+  /* The pipelined kernel fills a u16 j-cache by probing and reads any jbuf
+   * of at least n_grid entries that way, whichever mode sized it; mode 2
+   * as a sample-scatter map is the wave kernel's alone. */
   bool use_pipe = false;
   if ((plan->func == VMF_RATE || plan->func == VMF_DERIV_FAST) && b.n_wave &&
-      b.max_wave_len <= (uint32_t)(PIPE_CHUNKS * WAVE) && plan->pre_func == 0 &&
+      b.max_wave_len <= (uint32_t)(PIPE_PCHUNKS * 2 * WAVE) &&
+      plan->pre_func == 0 &&
       plan->window > 0 && plan->step > 0 && plan->window % plan->step == 0 &&
       n_grid > 1) {
     static int pipe_disabled = -1;
@@ -3750,9 +3509,6 @@ int vmgpu_rollup_exec(const vmgpu_plan* plan, uint64_t handle,
       const char* e = getenv("VMGPU_DISABLE_PIPE");
       pipe_disabled = (e && e[0] == '1') ? 1 : 0;
     }
-#ifdef VMGPU_ABL_GACC
-    pipe_disabled = 1; /* the GACC A/B runs through the wave kernel */
-#endif
     use_pipe = !pipe_disabled;
   }
   p.jbuf_elems = 0;
@@ -3765,26 +3521,7 @@ int vmgpu_rollup_exec(const vmgpu_plan* plan, uint64_t handle,
     int64_t dgp = (plan->window > 0 && plan->step > 0 &&
                    plan->window % plan->step == 0)
                       ? plan->window / plan->step : 0;
-    /* A/B measured (round 2): the in-scan J scatter costs MORE inside the
-     * staging chain (+0.46 ms at config 2) than the probe j-cache it
-     * replaces (~0.42 ms in an overlappable phase) — the divergent range
-     * writes and boundary fixups sit on the serial scan path.  Probe mode
-     * stays the default; VMGPU_PIPE_SCATTER=1 re-enables the scatter. */
-#ifdef VMGPU_PIPE_SCATTER
-    static int pipe_scatter = -1;
-    if (pipe_scatter < 0) {
-      const char* e2 = getenv("VMGPU_PIPE_SCATTER");
-      pipe_scatter = (e2 && e2[0] == '1') ? 1 : 0;
-    }
-#else
-    const int pipe_scatter = 0;
-#endif
-    if (use_pipe && pipe_scatter && dgp > 0 && n_grid + dgp <= 32000 &&
-        base + WAVES_PER_BLOCK * vm_jbuf_bytes(2, (int32_t)(n_grid + dgp)) <=
-            64 * 1024) {
-      p.jbuf_mode = 2;
-      p.jbuf_elems = (int32_t)(n_grid + dgp);
-    } else if (n_grid <= 4096 &&
+    if (n_grid <= 4096 &&
         base + WAVES_PER_BLOCK * vm_jbuf_bytes(1, n_grid) <= 64 * 1024) {
       p.jbuf_mode = 1;
       p.jbuf_elems = n_grid;
