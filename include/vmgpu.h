@@ -411,6 +411,43 @@ int vmgpu_batch_create_packed(
     uint64_t* out_handle, uint64_t* out_offsets,
     char* errbuf, size_t errbuf_len);
 
+/* histogram_over_time (rollupHistogram, rollup.go:1525) over a resident
+ * batch.  Unlike vmgpu_rollup_exec the output is SPARSE: one row per
+ * (series, vmrange bucket) that is non-zero at one or more grid points.
+ *
+ * vmgpu_vmrange_thresholds_set: uploads the 487-entry threshold table of
+ *   the vmrange step function (entry j = the smallest double whose bucket
+ *   code is >= j + 1; positive, strictly increasing).  The host builds it
+ *   once from its own bucket arithmetic so device classification is
+ *   bit-for-bit the host's; it holds for the library context and must be
+ *   set before the first exec.
+ * vmgpu_histogram_over_time_exec: grid [start:end:step], window = the range
+ *   selector's literal duration in ms.  Grid point g owns the samples with
+ *   t_end[g] - window < ts <= t_end[g].  drop_stale removes Prometheus
+ *   stale NaNs first (neither scanned nor bucketed).  Runs the mark pass,
+ *   the row scan and the count pass, returns the row count and
+ *   samplesScanned (sum of window lengths), and leaves the result resident
+ *   on the batch, replacing any earlier histogram result there
+ *   (vmgpu_batch_destroy frees it; vmgpu_rollup_exec's outputs are not
+ *   touched).  window <= 0, step <= 0 and end < start are errors.
+ * vmgpu_histogram_over_time_fetch: downloads the last result.  Rows are
+ *   ordered by series — the physical (group-contiguous) order for
+ *   relayouted grouped batches — then by ascending bucket code;
+ *   row_series[n_rows]
+ *   holds ORIGINAL series ids, row_bucket[n_rows] the code (0 = lower,
+ *   1..486 = bucket idx 0..485, 487 = upper), out[n_rows x n_grid] the
+ *   count as f64, NaN where it is zero.  Any destination may be NULL. */
+int vmgpu_vmrange_thresholds_set(const double* thresholds, uint32_t n,
+                                 char* errbuf, size_t errbuf_len);
+int vmgpu_histogram_over_time_exec(uint64_t handle, int64_t start, int64_t end,
+                                   int64_t step, int64_t window,
+                                   int32_t drop_stale, uint64_t* out_n_rows,
+                                   uint64_t* out_samples_scanned,
+                                   char* errbuf, size_t errbuf_len);
+int vmgpu_histogram_over_time_fetch(uint64_t handle, uint32_t* row_series,
+                                    uint16_t* row_bucket, double* out,
+                                    char* errbuf, size_t errbuf_len);
+
 /* Pinned host buffers for PCIe-rate staging of payloads and results (the
  * cgo layer would pool these; hipHostMalloc/-Free underneath). */
 int vmgpu_host_alloc(uint64_t nbytes, void** out_ptr);

@@ -38,6 +38,7 @@
 #include <mutex>
 #include <vector>
 
+#include "batch_access.h"
 #include "devalloc.h"
 #include "rollup_device.h"
 #include "vm_div1e3.h"
@@ -2893,6 +2894,8 @@ struct Batch {
    * contiguous in HBM (locality for the grouped-run accumulation);
    * perm[i] = original series id of physical row i (empty = identity) */
   std::vector<uint32_t> perm;
+  /* histogram_over_time result + scratch (hot.hip), independent of d_out */
+  vm_hot_state hot;
 };
 
 struct Ctx {
@@ -2921,6 +2924,28 @@ hipError_t vm_dev_free_raw(void* p) {
 }
 
 hipStream_t vm_ctx_stream(void) { return g_ctx.stream; }
+
+/* batch_access.h */
+std::mutex& vm_ctx_mutex(void) { return g_ctx.mu; }
+bool vm_ctx_inited(void) { return g_ctx.inited; }
+int vm_batch_cols_get(uint64_t handle, vm_batch_cols* out) {
+  auto it = g_ctx.batches.find(handle);
+  if (it == g_ctx.batches.end()) return 1;
+  Batch& b = it->second;
+  out->d_ts = b.d_ts;
+  out->d_vals = b.d_vals;
+  out->d_offsets = b.d_offsets;
+  out->n_series = b.n_series;
+  out->n_samples = b.n_samples;
+  out->perm = b.perm.empty() ? nullptr : b.perm.data();
+  out->hot = &b.hot;
+  return 0;
+}
+void vm_ctx_events(hipEvent_t* ev_start, hipEvent_t* ev_stop) {
+  *ev_start = g_ctx.ev_start;
+  *ev_stop = g_ctx.ev_stop;
+}
+void vm_ctx_set_last_kernel_ms(double ms) { g_ctx.last_kernel_ms = ms; }
 
 namespace {
 
@@ -3061,6 +3086,7 @@ void free_batch(Batch& b) {
   (void)vm_dev_free(b.d_out);
   (void)vm_dev_free(b.d_counts);
   (void)vm_dev_free(b.d_scanned);
+  vm_hot_state_free(&b.hot);
   b = Batch();
 }
 
@@ -3096,6 +3122,7 @@ int vmgpu_shutdown(void) {
   if (!g_ctx.inited) return 0;
   for (auto& kv : g_ctx.batches) free_batch(kv.second);
   g_ctx.batches.clear();
+  vm_hot_shutdown();
   (void)hipEventDestroy(g_ctx.ev_start);
   (void)hipEventDestroy(g_ctx.ev_stop);
   (void)hipStreamDestroy(g_ctx.stream);

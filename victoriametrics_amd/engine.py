@@ -303,10 +303,34 @@ def init(device=0):
 
 
 def shutdown():
-    global _inited
+    global _inited, _vmrange_uploaded
     if _inited:
         _load_lib().vmgpu_shutdown()
         _inited = False
+        _vmrange_uploaded = False
+
+
+_vmrange_uploaded = False
+
+
+def _upload_vmrange_thresholds(lib):
+    """Hand the device classifier its threshold table (built from the host
+    bucket function, rollup_multi.vmrange_bucket_thresholds) once per
+    library context."""
+    global _vmrange_uploaded
+    if _vmrange_uploaded:
+        return
+    init()
+    from .rollup_multi import vmrange_bucket_thresholds
+    thr = np.ascontiguousarray(vmrange_bucket_thresholds(), dtype=np.float64)
+    errbuf = ctypes.create_string_buffer(256)
+    rc = lib.vmgpu_vmrange_thresholds_set(
+        thr.ctypes.data_as(ctypes.POINTER(ctypes.c_double)),
+        ctypes.c_uint32(len(thr)), errbuf, ctypes.c_size_t(len(errbuf)))
+    if rc != 0:
+        raise VmGpuError(f"vmgpu_vmrange_thresholds_set failed ({rc}): "
+                         f"{errbuf.value.decode()}")
+    _vmrange_uploaded = True
 
 
 class RollupPlan:
@@ -609,6 +633,47 @@ class SeriesBatch:
             orig[self._perm] = out
             out = orig
         return out, counts, scanned.value
+
+    def histogram_over_time(self, start, end, step, window, drop_stale=True):
+        """histogram_over_time(m[window]) over every series of the batch, on
+        the device (csrc/hot.hip: mark pass, row scan, count pass).  The
+        output is sparse: one row per (series, vmrange bucket) that is
+        non-zero at one or more grid points, ordered by series (in the
+        batch's physical order for group-relayouted batches) and then by
+        ascending bucket code (0 = lower, 1..486 = bucket idx 0..485,
+        487 = upper).  Returns (row_series u32[n_rows] of ORIGINAL series
+        ids, row_bucket u16[n_rows], values f64[n_rows, n_grid] with NaN
+        where the count is zero, samples_scanned).  Raises VmGpuError
+        without a device or library; there is no CPU fallback."""
+        lib = _load_lib()
+        _upload_vmrange_thresholds(lib)
+        n_grid = 1 + (int(end) - int(start)) // int(step) if step > 0 else 0
+        n_rows = ctypes.c_uint64(0)
+        scanned = ctypes.c_uint64(0)
+        errbuf = ctypes.create_string_buffer(256)
+        rc = lib.vmgpu_histogram_over_time_exec(
+            ctypes.c_uint64(self.handle), ctypes.c_int64(int(start)),
+            ctypes.c_int64(int(end)), ctypes.c_int64(int(step)),
+            ctypes.c_int64(int(window)), ctypes.c_int32(1 if drop_stale else 0),
+            ctypes.byref(n_rows), ctypes.byref(scanned), errbuf,
+            ctypes.c_size_t(len(errbuf)))
+        if rc != 0:
+            raise VmGpuError(f"vmgpu_histogram_over_time_exec failed ({rc}): "
+                             f"{errbuf.value.decode()}")
+        rows = n_rows.value
+        row_series = np.empty(rows, dtype=np.uint32)
+        row_bucket = np.empty(rows, dtype=np.uint16)
+        values = np.empty((rows, n_grid), dtype=np.float64)
+        rc = lib.vmgpu_histogram_over_time_fetch(
+            ctypes.c_uint64(self.handle),
+            row_series.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)),
+            row_bucket.ctypes.data_as(ctypes.POINTER(ctypes.c_uint16)),
+            values.ctypes.data_as(ctypes.POINTER(ctypes.c_double)),
+            errbuf, ctypes.c_size_t(len(errbuf)))
+        if rc != 0:
+            raise VmGpuError(f"vmgpu_histogram_over_time_fetch failed ({rc}): "
+                             f"{errbuf.value.decode()}")
+        return row_series, row_bucket, values, scanned.value
 
     def fetch_out_into(self, dst, n_grid):
         """Download the last exec's output rows directly into a caller

@@ -4,9 +4,17 @@
 number of output series per input series — one per observed formatted value
 / non-zero vmrange bucket — via the timeseriesMap side channel
 (newTimeseriesMap, rollup.go:629; DoTimeseriesMap, rollup.go:700).  They do
-not fit the one-value-per-(series, grid point) kernel contract, so they run
-host-side exactly where the reference computes them, over the decoded
-columns; the per-point windows are the doInternal windows
+not fit the one-value-per-(series, grid point) kernel contract.
+
+`histogram_over_time` has a device path over a resident SeriesBatch
+(`histogram_over_time_batch` -> SeriesBatch.histogram_over_time -> the
+sparse two-pass kernels of csrc/hot.hip): its bucket set is bounded (488
+vmrange codes), so rows can be counted, scanned and filled on the GPU.  The
+per-column host function below stays as the reference and as the path for
+callers that have no batch.  `count_values_over_time` has NO device path:
+its output keys are formatted strings over an unbounded value set, so it
+runs host-side exactly where the reference computes it, over the decoded
+columns.  The per-point windows are the doInternal windows
 (seekFirstTimestampIdxAfter semantics) for an explicit lookbehind window.
 
 Neither function is in rollupFuncsCanAdjustWindow, so the window is the
@@ -153,3 +161,105 @@ def histogram_over_time(ts_col, vals_col, mn, start, end, step, window,
                 order.append(vmrange)
             s.values[g] = float(count)
     return [out[k] for k in order], scanned
+
+
+# --- device path of histogram_over_time -----------------------------------
+
+VMRANGE_N_THRESHOLDS = 487
+VMRANGE_CODE_UPPER = 487
+
+
+def _vmrange_code(v):
+    """Class of v under _histogram_update: None = contributes nothing,
+    0 = lower, 1..486 = bucket idx 0..485, 487 = upper."""
+    b = {}
+    _histogram_update(b, float(v))
+    if not b:
+        return None
+    key = next(iter(b))
+    if key == "lower":
+        return 0
+    if key == "upper":
+        return VMRANGE_CODE_UPPER
+    return key + 1
+
+
+_vmrange_thresholds = None
+
+
+def vmrange_bucket_thresholds():
+    """The 487 thresholds of the vmrange step function: entry j is the
+    smallest double whose code is >= j + 1, found by bisecting on the bit
+    pattern against _histogram_update itself (the formula is not restated
+    here), so code(v) = #{j : thr[j] <= v} for every non-negative double.
+    This table is what the device classifier uses (csrc/vmrange_bucket.h);
+    the host function is monotone in v, which tests/
+    test_vmrange_bucket_table.py checks around every threshold."""
+    global _vmrange_thresholds
+    if _vmrange_thresholds is None:
+        one = np.empty(1, dtype=np.uint64)
+
+        def at(bits):
+            one[0] = bits
+            return _vmrange_code(one.view(np.float64)[0])
+
+        inf_bits = int(np.float64(np.inf).view(np.uint64))
+        thr = np.empty(VMRANGE_N_THRESHOLDS, dtype=np.uint64)
+        lo_bound = 1  # smallest subnormal: code 0
+        for k in range(1, VMRANGE_N_THRESHOLDS + 1):
+            # invariant: code(lo) < k <= code(hi)
+            lo, hi = lo_bound, inf_bits
+            while hi - lo > 1:
+                mid = (lo + hi) // 2
+                if at(mid) >= k:
+                    hi = mid
+                else:
+                    lo = mid
+            thr[k - 1] = hi
+            lo_bound = lo
+        _vmrange_thresholds = thr.view(np.float64)
+        _vmrange_thresholds.setflags(write=False)
+    return _vmrange_thresholds
+
+
+def vmrange_code_lookup(v, thresholds=None):
+    """Table-lookup twin of _vmrange_code — the arithmetic the device
+    classifier performs."""
+    v = float(v)
+    if v != v or v < 0:
+        return None
+    thr = vmrange_bucket_thresholds() if thresholds is None else thresholds
+    return int(np.searchsorted(thr, v, side="right"))
+
+
+def vmrange_label(code):
+    if code == 0:
+        return _H_LOWER
+    if code == VMRANGE_CODE_UPPER:
+        return _H_UPPER
+    return _histogram_ranges()[code - 1]
+
+
+def histogram_over_time_batch(batch, metric_names, start, end, step, window,
+                              keep_metric_names=False, drop_stale=True):
+    """histogram_over_time over every series of a resident SeriesBatch in
+    one device call.  metric_names[s] is the MetricName of series s.
+    Returns (list[Series], samples_scanned); series come out ordered by
+    (series id, ascending vmrange bucket) — the reference's order is Go map
+    order and carries no meaning.  Naming is the host function's: the
+    metric group resets unless keep_metric_names, any existing vmrange tag
+    is replaced."""
+    row_series, row_bucket, values, scanned = batch.histogram_over_time(
+        start, end, step, window, drop_stale=drop_stale)
+    out = []
+    bases = {}
+    for i in np.argsort(row_series, kind="stable"):
+        s = int(row_series[i])
+        base = bases.get(s)
+        if base is None:
+            base = bases[s] = _base_mn(metric_names[s], keep_metric_names)
+        m2 = base.copy()
+        m2.remove_tag("vmrange")
+        m2.add_tag("vmrange", vmrange_label(int(row_bucket[i])))
+        out.append(Series(m2, values[i]))
+    return out, scanned
