@@ -448,6 +448,41 @@ int vmgpu_histogram_over_time_fetch(uint64_t handle, uint32_t* row_series,
                                     uint16_t* row_bucket, double* out,
                                     char* errbuf, size_t errbuf_len);
 
+/* count_values_over_time (newRollupCountValues, rollup.go:1490) over a
+ * resident batch.  The output is SPARSE like the histogram's: one row per
+ * (series, distinct value among the samples that lie in one or more
+ * windows).  Two values are distinct when their bits differ, except that
+ * every NaN is one value — exactly when strconv.FormatFloat(v,'g',-1,64),
+ * the reference's key, differs; the caller formats one label per row.
+ *
+ * vmgpu_count_values_over_time_exec: grid, window and drop_stale as in
+ *   vmgpu_histogram_over_time_exec (with drop_stale = 0 stale NaNs are
+ *   counted under NaN).  Runs the mark/sort pass, the row scan and the
+ *   count pass, returns the row count and samplesScanned, and leaves the
+ *   result resident on the batch, replacing any earlier count_values
+ *   result there; a histogram result on the same batch and
+ *   vmgpu_rollup_exec's outputs are not touched.  max_rows > 0 bounds the
+ *   row count (all-distinct gauges give one row per sample): above it the
+ *   call fails with both numbers in errbuf, allocates no result and leaves
+ *   none, so a later fetch fails too; 0 = unlimited.  window <= 0,
+ *   step <= 0, end < start and a grid above 2^30 points are errors.
+ * vmgpu_count_values_over_time_fetch: downloads the last result.  Rows are
+ *   ordered by series — the physical (group-contiguous) order for
+ *   relayouted grouped batches — then by ascending value,
+ *   -Inf ... -0 < 0 ... +Inf < NaN.  row_series[n_rows] holds ORIGINAL
+ *   series ids, row_value[n_rows] the counted value with its original bits
+ *   (0x7FF8000000000000 for NaN), out[n_rows x n_grid] the count as f64,
+ *   NaN where it is zero.  Any destination may be NULL. */
+int vmgpu_count_values_over_time_exec(uint64_t handle, int64_t start, int64_t end,
+                                      int64_t step, int64_t window,
+                                      int32_t drop_stale, uint64_t max_rows,
+                                      uint64_t* out_n_rows,
+                                      uint64_t* out_samples_scanned,
+                                      char* errbuf, size_t errbuf_len);
+int vmgpu_count_values_over_time_fetch(uint64_t handle, uint32_t* row_series,
+                                       double* row_value, double* out,
+                                       char* errbuf, size_t errbuf_len);
+
 /* Pinned host buffers for PCIe-rate staging of payloads and results (the
  * cgo layer would pool these; hipHostMalloc/-Free underneath). */
 int vmgpu_host_alloc(uint64_t nbytes, void** out_ptr);

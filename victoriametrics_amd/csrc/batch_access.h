@@ -29,6 +29,31 @@ struct vm_hot_state {
   unsigned long long* d_scanned = nullptr;
 };
 
+/* count_values_over_time state of a batch (cvot.hip), independent of the
+ * histogram state: both results can be resident at once.  Same ownership
+ * and grow-only rule (vm_cvot_state_free). */
+struct vm_cvot_state {
+  /* result */
+  double* d_out = nullptr;          /* [n_rows x n_grid] */
+  uint32_t* d_row_series = nullptr; /* [n_rows] PHYSICAL series row */
+  double* d_row_value = nullptr;    /* [n_rows] the counted value */
+  size_t out_cap = 0, row_series_cap = 0, row_value_cap = 0; /* bytes */
+  uint64_t n_rows = 0;
+  int32_t n_grid = 0;
+  bool valid = false;
+  /* scratch, sized by the batch */
+  uint32_t* d_local_row = nullptr;  /* [n_samples] row of the sample within
+                                     * its series, or CVOT_ROW_NONE */
+  uint64_t* d_row_keys = nullptr;   /* [n_samples] series s keeps its sorted
+                                     * distinct order keys at offsets[s]; a
+                                     * series too long for LDS sorts here */
+  uint32_t* d_row_counts = nullptr; /* [n_series] */
+  uint64_t* d_row_start = nullptr;  /* [n_series + 1] */
+  uint32_t* d_long_list = nullptr;  /* [n_series] series above the wave cap */
+  unsigned long long* d_small = nullptr; /* [0] samples scanned,
+                                          * [1] low word: long-list length */
+};
+
 struct vm_batch_cols {
   const int64_t* d_ts;
   const double* d_vals;
@@ -38,6 +63,7 @@ struct vm_batch_cols {
   const uint32_t* perm;      /* host; physical row -> original series id,
                               * NULL = identity */
   vm_hot_state* hot;
+  vm_cvot_state* cvot;
 };
 
 std::mutex& vm_ctx_mutex(void);
@@ -50,6 +76,9 @@ void vm_ctx_set_last_kernel_ms(double ms);
 
 /* hot.hip: release every buffer of a batch's histogram state */
 void vm_hot_state_free(vm_hot_state* h);
+
+/* cvot.hip: release every buffer of a batch's count_values state */
+void vm_cvot_state_free(vm_cvot_state* h);
 
 /* hot.hip: drop the uploaded threshold table (called from vmgpu_shutdown
  * with the context lock held) */

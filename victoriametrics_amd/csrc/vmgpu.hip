@@ -2896,6 +2896,8 @@ struct Batch {
   std::vector<uint32_t> perm;
   /* histogram_over_time result + scratch (hot.hip), independent of d_out */
   vm_hot_state hot;
+  /* count_values_over_time result + scratch (cvot.hip) */
+  vm_cvot_state cvot;
 };
 
 struct Ctx {
@@ -2939,6 +2941,7 @@ int vm_batch_cols_get(uint64_t handle, vm_batch_cols* out) {
   out->n_samples = b.n_samples;
   out->perm = b.perm.empty() ? nullptr : b.perm.data();
   out->hot = &b.hot;
+  out->cvot = &b.cvot;
   return 0;
 }
 void vm_ctx_events(hipEvent_t* ev_start, hipEvent_t* ev_stop) {
@@ -3087,6 +3090,7 @@ void free_batch(Batch& b) {
   (void)vm_dev_free(b.d_counts);
   (void)vm_dev_free(b.d_scanned);
   vm_hot_state_free(&b.hot);
+  vm_cvot_state_free(&b.cvot);
   b = Batch();
 }
 

@@ -675,6 +675,50 @@ class SeriesBatch:
                              f"{errbuf.value.decode()}")
         return row_series, row_bucket, values, scanned.value
 
+    def count_values_over_time(self, start, end, step, window,
+                               drop_stale=True, max_rows=0):
+        """count_values_over_time(m[window]) over every series of the batch,
+        on the device (csrc/cvot.hip: mark/sort pass, row scan, count pass).
+        The output is sparse: one row per (series, distinct value among the
+        samples that lie in at least one window), every NaN counted as one
+        value.  Rows are ordered by series (in the batch's physical order
+        for group-relayouted batches) and then by ascending value,
+        -Inf ... -0 < 0 ... +Inf < NaN (rollup_multi.count_values_order_key).
+        Returns (row_series u32[n_rows] of ORIGINAL series ids, row_value
+        f64[n_rows], values f64[n_rows, n_grid] with NaN where the count is
+        zero, samples_scanned).  max_rows > 0 bounds n_rows: above it the
+        call raises and leaves no result.  Raises VmGpuError without a
+        device or library; there is no CPU fallback."""
+        lib = _load_lib()
+        init()
+        n_grid = 1 + (int(end) - int(start)) // int(step) if step > 0 else 0
+        n_rows = ctypes.c_uint64(0)
+        scanned = ctypes.c_uint64(0)
+        errbuf = ctypes.create_string_buffer(256)
+        rc = lib.vmgpu_count_values_over_time_exec(
+            ctypes.c_uint64(self.handle), ctypes.c_int64(int(start)),
+            ctypes.c_int64(int(end)), ctypes.c_int64(int(step)),
+            ctypes.c_int64(int(window)), ctypes.c_int32(1 if drop_stale else 0),
+            ctypes.c_uint64(int(max_rows)), ctypes.byref(n_rows),
+            ctypes.byref(scanned), errbuf, ctypes.c_size_t(len(errbuf)))
+        if rc != 0:
+            raise VmGpuError("vmgpu_count_values_over_time_exec failed "
+                             f"({rc}): {errbuf.value.decode()}")
+        rows = n_rows.value
+        row_series = np.empty(rows, dtype=np.uint32)
+        row_value = np.empty(rows, dtype=np.float64)
+        values = np.empty((rows, n_grid), dtype=np.float64)
+        rc = lib.vmgpu_count_values_over_time_fetch(
+            ctypes.c_uint64(self.handle),
+            row_series.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)),
+            row_value.ctypes.data_as(ctypes.POINTER(ctypes.c_double)),
+            values.ctypes.data_as(ctypes.POINTER(ctypes.c_double)),
+            errbuf, ctypes.c_size_t(len(errbuf)))
+        if rc != 0:
+            raise VmGpuError("vmgpu_count_values_over_time_fetch failed "
+                             f"({rc}): {errbuf.value.decode()}")
+        return row_series, row_value, values, scanned.value
+
     def fetch_out_into(self, dst, n_grid):
         """Download the last exec's output rows directly into a caller
         buffer (e.g. a marshal buffer's values section) — no intermediate

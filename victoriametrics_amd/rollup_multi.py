@@ -6,16 +6,20 @@ number of output series per input series — one per observed formatted value
 (newTimeseriesMap, rollup.go:629; DoTimeseriesMap, rollup.go:700).  They do
 not fit the one-value-per-(series, grid point) kernel contract.
 
-`histogram_over_time` has a device path over a resident SeriesBatch
-(`histogram_over_time_batch` -> SeriesBatch.histogram_over_time -> the
-sparse two-pass kernels of csrc/hot.hip): its bucket set is bounded (488
-vmrange codes), so rows can be counted, scanned and filled on the GPU.  The
-per-column host function below stays as the reference and as the path for
-callers that have no batch.  `count_values_over_time` has NO device path:
-its output keys are formatted strings over an unbounded value set, so it
-runs host-side exactly where the reference computes it, over the decoded
-columns.  The per-point windows are the doInternal windows
-(seekFirstTimestampIdxAfter semantics) for an explicit lookbehind window.
+Both have a device path over a resident SeriesBatch, on the same sparse
+contract (mark pass, row scan, count pass):
+`histogram_over_time_batch` -> SeriesBatch.histogram_over_time ->
+csrc/hot.hip keys rows on the 488 vmrange codes;
+`count_values_over_time_batch` -> SeriesBatch.count_values_over_time ->
+csrc/cvot.hip keys rows on the value's bits.  The reference's key,
+strconv.FormatFloat(v,'g',-1,64), is the shortest round-trip form: a pure
+function of the bits, injective on non-NaN doubles (-0 and 0 differ) and
+"NaN" for every NaN.  So the device finds a series' distinct values with a
+sort over canonicalised bits and the host formats one label per output row,
+not one per sample.  The per-column host functions below stay as the
+references and as the path for callers that have no batch.  The per-point
+windows are the doInternal windows (seekFirstTimestampIdxAfter semantics)
+for an explicit lookbehind window.
 
 Neither function is in rollupFuncsCanAdjustWindow, so the window is the
 range selector's literal duration (required: both take m[d]).  Neither is
@@ -261,5 +265,57 @@ def histogram_over_time_batch(batch, metric_names, start, end, step, window,
         m2 = base.copy()
         m2.remove_tag("vmrange")
         m2.add_tag("vmrange", vmrange_label(int(row_bucket[i])))
+        out.append(Series(m2, values[i]))
+    return out, scanned
+
+
+# --- device path of count_values_over_time --------------------------------
+
+_NAN_BITS = 0x7FF8000000000000
+
+
+def count_values_order_key(v):
+    """The u64 by which the device orders (and tells apart) the values of
+    one series — host twin of cvot_order_key in csrc/cvot.hip.  On the
+    value's bits u, every NaN first mapped to 0x7FF8000000000000:
+    (u >> 63) ? ~u : u | 1 << 63.  Unsigned-ascending is
+    -Inf ... -0 < 0 ... +Inf < NaN; equal keys <=> equal 'g' labels."""
+    u = int(np.asarray(v, dtype=np.float64).reshape(1).view(np.uint64)[0])
+    if (u & 0x7FFFFFFFFFFFFFFF) > 0x7FF0000000000000:
+        u = _NAN_BITS
+    if u >> 63:
+        return ~u & 0xFFFFFFFFFFFFFFFF
+    return u | (1 << 63)
+
+
+def count_values_over_time_batch(label_name, batch, metric_names, start, end,
+                                 step, window, keep_metric_names=False,
+                                 drop_stale=True, max_rows=None):
+    """count_values_over_time over every series of a resident SeriesBatch in
+    one device call.  metric_names[s] is the MetricName of series s.
+    Returns (list[Series], samples_scanned); series come out ordered by
+    (series id, ascending value) — the reference's order is Go map order and
+    carries no meaning.  Naming is the host function's: the metric group
+    resets unless keep_metric_names, any existing label_name tag is
+    replaced, the label value is format_go_float_g of the row's value (one
+    call per row).  max_rows bounds the number of output series; None takes
+    limits.max_series_per_aggr_func, the flag the reference applies to
+    count_values, 0 is unlimited.  Above the bound the device call raises
+    VmGpuError before it allocates any output."""
+    if max_rows is None:
+        from . import limits
+        max_rows = limits.max_series_per_aggr_func
+    row_series, row_value, values, scanned = batch.count_values_over_time(
+        start, end, step, window, drop_stale=drop_stale, max_rows=max_rows)
+    out = []
+    bases = {}
+    for i in np.argsort(row_series, kind="stable"):
+        s = int(row_series[i])
+        base = bases.get(s)
+        if base is None:
+            base = bases[s] = _base_mn(metric_names[s], keep_metric_names)
+        m2 = base.copy()
+        m2.remove_tag(label_name)
+        m2.add_tag(label_name, format_go_float_g(float(row_value[i])))
         out.append(Series(m2, values[i]))
     return out, scanned
