@@ -6,11 +6,11 @@ cd "$(dirname "$0")"
 FLAGS="--offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off -fPIC"
 mkdir -p .abl
 
-# rollup path only (the bench exercises nothing else) — keeps the libs small
+# the same sources as build.sh: vmgpu.hip refers to every one of them
 build_one() {
   name=$1
   shift
-  hipcc $FLAGS "$@" -shared vmgpu.hip decode.hip binop.hip transform.hip aggrcol.hip -o ../libvmgpu_$name.so
+  hipcc $FLAGS "$@" -shared vmgpu.hip decode.hip binop.hip transform.hip aggrcol.hip hot.hip cvot.hip -o ../libvmgpu_$name.so
 }
 
 build_one pipe_stage -DVMGPU_PIPE_ABL_STAGE &
@@ -32,5 +32,11 @@ build_one pipe_nodtfast -DVMGPU_PIPE_DT_FAST=0 &
 build_one pipe_nopmaxskip -DVMGPU_PIPE_SKIP_PMAX=0 &
 build_one pipe_nocuts -DVMGPU_PIPE_SENTINEL=0 -DVMGPU_PIPE_HINT_ACC=0 \
   -DVMGPU_PIPE_DT_FAST=0 -DVMGPU_PIPE_SKIP_PMAX=0 &
+wait
+# latency cuts of the series loop, one off at a time (both on by default),
+# and both off
+build_one pipe_nosdesc -DVMGPU_PIPE_SDESC=0 &
+build_one pipe_noasmload -DVMGPU_PIPE_ASMLOAD=0 &
+build_one pipe_noprefetch -DVMGPU_PIPE_SDESC=0 -DVMGPU_PIPE_ASMLOAD=0 &
 wait
 echo "ablation libs built"

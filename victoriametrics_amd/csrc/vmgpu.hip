@@ -82,6 +82,22 @@
 #define VMGPU_PIPE_SKIP_PMAX 1
 #endif
 
+/* Latency cuts of the pipe kernel's series loop (profiles/pipe_prefetch.md),
+ * gated the same way; none changes an output bit.
+ *   SDESC    the per-series descriptors (selection entry, offsets, scrape
+ *            interval) are read through the constant address space, so they
+ *            are scalar loads inside the loop too, and they are read two
+ *            series ahead (the selection entry three)
+ *   ASMLOAD  the staged b128 loads are inline asm the compiler does not
+ *            count: nothing waits for them until the one hand-placed wait
+ *            at the top of the next iteration */
+#ifndef VMGPU_PIPE_SDESC
+#define VMGPU_PIPE_SDESC 1
+#endif
+#ifndef VMGPU_PIPE_ASMLOAD
+#define VMGPU_PIPE_ASMLOAD 1
+#endif
+
 #define WAVE 64
 #define BLOCK_THREADS 256
 #define WAVES_PER_BLOCK (BLOCK_THREADS / WAVE)
@@ -1197,9 +1213,14 @@ __global__ __launch_bounds__(BLOCK_THREADS) void rollup_wave_kernel(KPlan p, KIO
 /*     writing the corrected pair-interleaved slab to LDS (no LDS     */
 /*     re-read pass),                                                 */
 /*   - the NEXT series' loads are issued as soon as the registers die,*/
-/*     overlapping scrape/seek/eval/emit of the current series,       */
+/*     overlapping scrape/seek/eval/emit of the current series; they  */
+/*     are inline asm, so the compiler inserts no wait for them, and  */
+/*     the one hand-placed wait sits at the top of the next iteration,*/
+/*   - the per-series descriptors are scalar loads issued two series  */
+/*     ahead (pipe_desc_read),                                        */
 /*   - every phase barrier is lgkm-only (wave_ds_sync), so the        */
-/*     prefetched loads stay outstanding across the whole evaluation. */
+/*     prefetched loads stay outstanding across the whole evaluation  */
+/*     and the back edge.                                             */
 /* Results are bit-identical to the wave kernel: same scan, same      */
 /* j-cache seeks, same evaluators.                                    */
 /* ------------------------------------------------------------------ */
@@ -1473,6 +1494,112 @@ static VM_DEV int rcr_scan_pairs(const int64_t* t0a, const int64_t* t1a,
   return (int)n;
 }
 
+/* Per-series descriptor of the pipe kernel's series loop: the series index,
+ * its sample range and its precomputed scrape interval.  All wave-uniform. */
+struct PipeDesc {
+  uint32_t s;
+  uint64_t lo, hi; /* samples [lo, hi); the count is taken at the point of
+                      use so that nothing waits for the loads when issued */
+  int64_t si_raw;
+  int32_t grp;     /* grouped instantiation only; -1 = no group */
+  __device__ int64_t n() const { return (int64_t)(hi - lo); }
+};
+
+/* The selection list, the offsets, the scrape intervals and the group ids
+ * are never written while a rollup kernel runs, so they may be read through
+ * the constant address space: the compiler then emits scalar loads even after
+ * the kernel's first store (it cannot prove that the output rows do not
+ * alias a plain global pointer, and falls back to vector loads with a
+ * vmcnt wait).  Callers pass wave-uniform indices only. */
+#if VMGPU_PIPE_SDESC
+#define VM_PIPE_RO __attribute__((address_space(4)))
+#else
+#define VM_PIPE_RO
+#endif
+
+static VM_DEV uint32_t pipe_sel(const KIO& io, uint32_t w) {
+  if (!io.series_sel) return w;
+  return __builtin_amdgcn_readfirstlane(
+      ((const VM_PIPE_RO uint32_t*)io.series_sel)[w]);
+}
+
+template <bool GROUPED>
+static VM_DEV void pipe_desc_read(const KIO& io, uint32_t s, PipeDesc& d) {
+  const VM_PIPE_RO uint64_t* off = (const VM_PIPE_RO uint64_t*)io.offsets;
+  d.s = s;
+  d.lo = off[s];
+  d.hi = off[s + 1];
+  d.si_raw = io.series_si ? ((const VM_PIPE_RO int64_t*)io.series_si)[s] : 0;
+  d.grp = -1;
+  if constexpr (GROUPED) {
+    if (io.group_ids) d.grp = ((const VM_PIPE_RO int32_t*)io.group_ids)[s];
+  }
+}
+
+/* The staged loads of one series: one b128 per column per 128-sample chunk,
+ * lane l taking samples (2l, 2l+1), the index clamped to the last pair (the
+ * batch columns carry 16 B slack for that).  Issued only for a non-empty
+ * series at an even sample offset.
+ *
+ * ASMLOAD: the four loads are inline asm, so the compiler neither counts
+ * them nor waits for them; pipe_stage_wait below is the only wait, and
+ * nothing may read qt/qv between the two (audit the ISA after an edit for a
+ * v_mov or a spill of those registers: the destinations count as written
+ * when the statement ends, not when the data lands).  Early-clobber
+ * outputs: a destination must not share registers with the lane offsets the
+ * later loads of the same statement still read.  The leading s_nop covers a
+ * base pointer written by a VALU (v_readfirstlane) just before. */
+typedef int64_t vm_i64v2 __attribute__((ext_vector_type(2)));
+typedef double vm_f64v2 __attribute__((ext_vector_type(2)));
+
+static VM_DEV void pipe_stage_issue(vm_i64v2 (&qt)[PIPE_PCHUNKS],
+                                    vm_f64v2 (&qv)[PIPE_PCHUNKS],
+                                    const int64_t* gts, const double* gvs,
+                                    int64_t n, int lane) {
+  static_assert(PIPE_PCHUNKS == 2, "pipe_stage_issue names two chunks");
+  const int64_t nm2 = (n - 1) & ~(int64_t)1;
+  int64_t k0 = 2 * lane;
+  int64_t k1 = 2 * WAVE + 2 * lane;
+  if (k0 > nm2) k0 = nm2;
+  if (k1 > nm2) k1 = nm2;
+#if VMGPU_PIPE_ASMLOAD
+  const uint32_t o0 = (uint32_t)k0 * 8u;
+  const uint32_t o1 = (uint32_t)k1 * 8u;
+  const int64_t* bts = (const int64_t*)vm_uniform_i64((int64_t)gts);
+  const double* bvs = (const double*)vm_uniform_i64((int64_t)gvs);
+  asm volatile(
+      "s_nop 4\n\t"
+      "global_load_dwordx4 %0, %4, %6\n\t"
+      "global_load_dwordx4 %1, %4, %7\n\t"
+      "global_load_dwordx4 %2, %5, %6\n\t"
+      "global_load_dwordx4 %3, %5, %7"
+      : "=&v"(qt[0]), "=&v"(qv[0]), "=&v"(qt[1]), "=&v"(qv[1])
+      : "v"(o0), "v"(o1), "s"(bts), "s"(bvs)
+      : "memory");
+#else
+  qt[0] = *(const vm_i64v2*)(gts + k0);
+  qv[0] = *(const vm_f64v2*)(gvs + k0);
+  qt[1] = *(const vm_i64v2*)(gts + k1);
+  qv[1] = *(const vm_f64v2*)(gvs + k1);
+#endif
+}
+
+/* Retires the staged loads before their first consumer.  vmcnt(0): the row
+ * stores of the previous series retire with them (a counted wait that left
+ * those stores in flight measured no faster, profiles/pipe_prefetch.md).
+ * The empty statement makes the registers opaque so that no consumer is
+ * scheduled above the wait. */
+static VM_DEV void pipe_stage_wait(vm_i64v2 (&qt)[PIPE_PCHUNKS],
+                                   vm_f64v2 (&qv)[PIPE_PCHUNKS]) {
+#if VMGPU_PIPE_ASMLOAD
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  asm volatile("" : "+v"(qt[0]), "+v"(qv[0]), "+v"(qt[1]), "+v"(qv[1])
+               :: "memory");
+#else
+  (void)qt; (void)qv;
+#endif
+}
+
 /* VMGPU_PIPE_MINWAVES forces an occupancy floor (waves/SIMD) on the pipe
  * kernel for A/B builds; VMGPU_PIPE_UNROLL (2 or 4) sets the eval ILP. */
 #ifndef VMGPU_PIPE_UNROLL
@@ -1531,56 +1658,60 @@ void rollup_pipe_kernel(KPlan p, KIO io) {
   const uint32_t wave_stride = gridDim.x * WAVES_PER_BLOCK;
 
   /* pair staging registers: lane l holds samples (2l, 2l+1) of each
-   * 128-sample chunk, loaded with ONE b128 per column per chunk */
+   * 128-sample chunk, loaded with ONE b128 per column per chunk.  qt/qv
+   * are the load destinations and are carried round the loop; rt0..rv1
+   * are their halves, valid from pipe_stage_wait to the end of staging. */
+  vm_i64v2 qt[PIPE_PCHUNKS];
+  vm_f64v2 qv[PIPE_PCHUNKS];
   int64_t rt0[PIPE_PCHUNKS], rt1[PIPE_PCHUNKS];
   double rv0[PIPE_PCHUNKS], rv1[PIPE_PCHUNKS];
 
   /* wave_id is wave-uniform by construction; readfirstlane makes that
-   * provable, so the per-series descriptor reads below become scalar
-   * (s_load, lgkm-counted) instead of divergent vector loads, and the
-   * staging loads below are unconditional with clamped indices — one
-   * basic block, so the compiler can track outstanding vmcnt precisely
-   * instead of falling back to vmcnt(0) at every use. */
+   * provable, so every descriptor below lives in scalar registers.  The
+   * loop is a three-deep software pipeline over this wave's series
+   * k, k+1, k+2, ...:
+   *   - descriptors are scalar loads (SDESC) issued two series ahead, right
+   *     behind the data prefetch, the selection entry one step before the
+   *     offsets that depend on it.  They are retired by the lgkmcnt(0) of
+   *     the phase barrier that follows, never by a vmcnt wait.  Without
+   *     SDESC they are vector loads + v_readfirstlane with a vmcnt(0) each.
+   *   - the data of series k+1 is loaded into qt/qv as soon as the scan of
+   *     series k has consumed them, and is waited for exactly once, at the
+   *     top of iteration k+1 (pipe_stage_wait).  With ASMLOAD nothing else
+   *     on the hot path waits on vmcnt: no drain before the prefetch issue
+   *     and none at the back edge. */
   uint32_t ws = __builtin_amdgcn_readfirstlane(wave_id);
-  uint32_t s = 0;
-  uint64_t lo = 0;
-  int64_t n = 0;
-  int64_t si_raw = 0;
-  if (ws < io.n_sel) {
-    s = __builtin_amdgcn_readfirstlane(io.series_sel ? io.series_sel[ws] : ws);
-    lo = io.offsets[s];
-    n = (int64_t)(io.offsets[s + 1] - lo);
-    if (io.series_si) si_raw = io.series_si[s];
-    if (n > 0 && (lo & 1) == 0) {
-      const int64_t* gts = io.ts + lo;
-      const double* gvs = io.vals + lo;
-      const int64_t nm2 = (n - 1) & ~(int64_t)1;
-#pragma unroll
-      for (int c = 0; c < PIPE_PCHUNKS; c++) {
-        int64_t k = (int64_t)c * 2 * WAVE + 2 * lane;
-        if (k > nm2) k = nm2; /* batch columns carry 16 B slack for this */
-        vm_i64x2 tp = *(const vm_i64x2*)(gts + k);
-        double2 vp = *(const double2*)(gvs + k);
-        rt0[c] = tp.x;
-        rt1[c] = tp.y;
-        rv0[c] = vp.x;
-        rv1[c] = vp.y;
-      }
-    }
+  PipeDesc cur = {0, 0, 0, 0, -1};
+  PipeDesc nxt = {0, 0, 0, 0, -1};
+  uint32_t s_nn = 0;
+  /* 64-bit positions: ws + 3 * wave_stride may pass 2^32 */
+  const uint64_t n_sel = io.n_sel;
+  if (ws < n_sel) {
+    pipe_desc_read<GROUPED>(io, pipe_sel(io, ws), cur);
+    if ((uint64_t)ws + wave_stride < n_sel)
+      pipe_desc_read<GROUPED>(io, pipe_sel(io, ws + wave_stride), nxt);
+    if ((uint64_t)ws + 2ull * wave_stride < n_sel)
+      s_nn = pipe_sel(io, ws + 2 * wave_stride);
+    if (cur.n() > 0 && (cur.lo & 1) == 0)
+      pipe_stage_issue(qt, qv, io.ts + cur.lo, io.vals + cur.lo, cur.n(),
+                       lane);
   }
-  while (ws < io.n_sel) {
+  while (ws < n_sel) {
+    const uint32_t s = cur.s;
+    const uint64_t lo = cur.lo;
+    const int64_t n = cur.n();
+    const int64_t si_raw = cur.si_raw;
     const uint32_t ws_n = ws + wave_stride;
-    const bool has_next = ws_n < io.n_sel;
-    uint32_t s_n = 0;
-    uint64_t lo_n = 0;
-    int64_t n_n = 0;
-    int64_t si_raw_n = 0;
-    if (has_next) {
-      s_n = __builtin_amdgcn_readfirstlane(
-          io.series_sel ? io.series_sel[ws_n] : ws_n);
-      lo_n = io.offsets[s_n];
-      n_n = (int64_t)(io.offsets[s_n + 1] - lo_n);
-      if (io.series_si) si_raw_n = io.series_si[s_n];
+    const bool has_next = (uint64_t)ws + wave_stride < n_sel;
+    const bool has_nn = (uint64_t)ws + 2ull * wave_stride < n_sel;
+    const bool has_nnn = (uint64_t)ws + 3ull * wave_stride < n_sel;
+    pipe_stage_wait(qt, qv);
+#pragma unroll
+    for (int c = 0; c < PIPE_PCHUNKS; c++) {
+      rt0[c] = qt[c].x;
+      rt1[c] = qt[c].y;
+      rv0[c] = qv[c].x;
+      rv1[c] = qv[c].y;
     }
     /* stage the current series into LDS from registers (rcr fused);
      * odd-offset series (no 16-B-aligned pair loads) fall to the global
@@ -1619,23 +1750,19 @@ void rollup_pipe_kernel(KPlan p, KIO io) {
       }
     }
     /* the staging registers are dead now — prefetch the NEXT series into
-     * them; these loads stay in flight across scrape/seek/eval/emit */
-    if (has_next && n_n > 0 && (lo_n & 1) == 0) {
-      const int64_t* gts = io.ts + lo_n;
-      const double* gvs = io.vals + lo_n;
-      const int64_t nm2 = (n_n - 1) & ~(int64_t)1;
-#pragma unroll
-      for (int c = 0; c < PIPE_PCHUNKS; c++) {
-        int64_t k = (int64_t)c * 2 * WAVE + 2 * lane;
-        if (k > nm2) k = nm2;
-        vm_i64x2 tp = *(const vm_i64x2*)(gts + k);
-        double2 vp = *(const double2*)(gvs + k);
-        rt0[c] = tp.x;
-        rt1[c] = tp.y;
-        rv0[c] = vp.x;
-        rv1[c] = vp.y;
-      }
-    }
+     * them; these loads stay in flight across scrape/seek/eval/emit and
+     * the back edge, up to pipe_stage_wait */
+    if (has_next && nxt.n() > 0 && (nxt.lo & 1) == 0)
+      pipe_stage_issue(qt, qv, io.ts + nxt.lo, io.vals + nxt.lo, nxt.n(),
+                       lane);
+    /* descriptors of the series after the next one, and the selection
+     * entry of the one after that.  Here and not earlier: an outstanding
+     * scalar load turns every counted lgkmcnt wait of the scan above into
+     * lgkmcnt(0); the phase barrier below is lgkmcnt(0) anyway. */
+    PipeDesc nn = {0, 0, 0, 0, -1};
+    uint32_t s_nnn = 0;
+    if (has_nn) pipe_desc_read<GROUPED>(io, s_nn, nn);
+    if (has_nnn) s_nnn = pipe_sel(io, ws_n + 2 * wave_stride);
     if (count < 0) {
       /* stale NaNs present or odd-offset series (rare): from global */
       count = load_compact_wave<2>(io.ts + lo, io.vals + lo, n, lts, lvs,
@@ -1659,11 +1786,11 @@ void rollup_pipe_kernel(KPlan p, KIO io) {
           count ? lvs[gc * 2] : 0.0;
     }
     wave_ds_sync();
+    if (!has_next) break;
     ws = ws_n;
-    s = s_n;
-    lo = lo_n;
-    n = n_n;
-    si_raw = si_raw_n;
+    cur = nxt;
+    nxt = nn;
+    s_nn = s_nnn;
     continue;
 #endif
 
@@ -1715,7 +1842,7 @@ void rollup_pipe_kernel(KPlan p, KIO io) {
     double* grp_vrow = nullptr;
     double* grp_crow = nullptr;
     if constexpr (GROUPED) {
-      int grp = io.group_ids ? io.group_ids[s] : -1;
+      const int grp = cur.grp;
       if (grp >= 0) {
         grp_vrow = io.out + (size_t)grp * (size_t)p.n_grid;
         grp_crow = io.out_counts + (size_t)grp * (size_t)p.n_grid;
@@ -1896,11 +2023,11 @@ void rollup_pipe_kernel(KPlan p, KIO io) {
      * samplesScannedPerCall (= 2 for rate/deriv_fast) */
     scanned += 2ull * (unsigned long long)p.n_grid;
     wave_ds_sync();
+    if (!has_next) break; /* ws_n may have wrapped */
     ws = ws_n;
-    s = s_n;
-    lo = lo_n;
-    n = n_n;
-    si_raw = si_raw_n;
+    cur = nxt;
+    nxt = nn;
+    s_nn = s_nnn;
   }
   if (lane == 0 && scanned) atomicAdd(io.samples_scanned, (unsigned long long)scanned);
 }
@@ -2795,6 +2922,70 @@ __global__ void hq_kernel(double phi, const double* bv, const double* les,
 /* launch dispatch: compile-time specialization for hot funcs         */
 /* ------------------------------------------------------------------ */
 
+/* Grid of the pipe kernel.  Every wave walks the series list with a
+ * grid-wide stride, so any grid from one block to one block per four series
+ * computes the same thing; what the grid decides is how long each wave's
+ * chain of series is.  Measured on the flagship batch (1M series, 250,000
+ * blocks needed, 1280 resident; profiles/pipe_prefetch.md section 3):
+ *   - exactly the resident count (one block per slot, 195 series a wave) is
+ *     the SLOWEST whole-residency grid, 1.58 ms: the launch ends with the
+ *     slowest CU and nothing rebalances;
+ *   - more, shorter blocks let the dispatcher rebalance: 1.45 ms at 4096,
+ *     1.39 ms at 8192, 1.37 ms at 16384 (grouped: 1.80 / 1.71 / 1.89);
+ *   - a grid between one and two residencies (1920) is slower than either,
+ *     and chains of fewer than about ten series (32768 blocks) are far
+ *     slower, 2.06 ms: each block pays an un-prefetched first series.
+ * Hence: whole residencies, as many as leave each wave PIPE_MIN_CHAIN
+ * series, at most PIPE_MAX_BLOCKS blocks.  The resident count is queried
+ * once per instantiation and LDS size.
+ *
+ * VMGPU_PIPE_BLOCKS=<n> overrides the grid within [1, blocks needed]; it is
+ * read at every launch, so tests can put many series on one wave and one
+ * library can be measured at several grids.  Anything that is not a plain
+ * integer is ignored. */
+#define PIPE_MIN_CHAIN 16
+#define PIPE_MAX_BLOCKS 8192
+
+template <int FUNC_CT, bool GROUPED>
+static uint32_t pipe_grid_blocks(uint32_t need, size_t lds) {
+  static std::mutex mu;
+  static std::map<size_t, uint32_t> resident_by_lds;
+  uint32_t resident = 0;
+  {
+    std::lock_guard<std::mutex> g(mu);
+    auto it = resident_by_lds.find(lds);
+    if (it != resident_by_lds.end()) {
+      resident = it->second;
+    } else {
+      int per_cu = 0, dev = 0;
+      hipDeviceProp_t prop;
+      if (hipOccupancyMaxActiveBlocksPerMultiprocessor(
+              &per_cu, rollup_pipe_kernel<FUNC_CT, GROUPED>, BLOCK_THREADS,
+              lds) == hipSuccess &&
+          hipGetDevice(&dev) == hipSuccess &&
+          hipGetDeviceProperties(&prop, dev) == hipSuccess && per_cu > 0 &&
+          prop.multiProcessorCount > 0)
+        resident = (uint32_t)per_cu * (uint32_t)prop.multiProcessorCount;
+      else
+        resident = MAX_WAVE_BLOCKS; /* no answer: the grid used before */
+      resident_by_lds[lds] = resident;
+    }
+  }
+  const uint32_t rounds = std::max<uint32_t>(
+      1, need / std::max<uint32_t>(1, resident * PIPE_MIN_CHAIN));
+  uint32_t blocks = (uint32_t)std::min<uint64_t>(
+      std::min<uint64_t>((uint64_t)resident * rounds, PIPE_MAX_BLOCKS), need);
+  blocks = std::max<uint32_t>(blocks, 1);
+  if (const char* e = getenv("VMGPU_PIPE_BLOCKS")) {
+    const long long cap = std::max<uint32_t>(need, 1);
+    char* end = nullptr;
+    long long v = strtoll(e, &end, 10);
+    if (end != e && *end == '\0')
+      blocks = (uint32_t)std::min<long long>(std::max<long long>(v, 1), cap);
+  }
+  return blocks;
+}
+
 template <int FUNC_CT>
 static void launch_rollup_t(int which, uint32_t blocks, size_t lds,
                             const KPlan& p, const KIO& w, hipStream_t stream) {
@@ -2815,14 +3006,18 @@ static void launch_rollup_t(int which, uint32_t blocks, size_t lds,
      * samples); instantiated only for the hot specializations it is
      * measured on — everything else falls back to the wave kernel */
     if constexpr (FUNC_CT == VMF_RATE || FUNC_CT == VMF_DERIV_FAST) {
+      /* `blocks` is the unclamped ceil(n_wave / WAVES_PER_BLOCK) here */
       if (p.aggr != VMGPU_AGGR_NONE && w.group_ids)
-        hipLaunchKernelGGL((rollup_pipe_kernel<FUNC_CT, true>), dim3(blocks),
+        hipLaunchKernelGGL((rollup_pipe_kernel<FUNC_CT, true>),
+                           dim3(pipe_grid_blocks<FUNC_CT, true>(blocks, lds)),
                            dim3(BLOCK_THREADS), lds, stream, p, w);
       else
-        hipLaunchKernelGGL((rollup_pipe_kernel<FUNC_CT, false>), dim3(blocks),
+        hipLaunchKernelGGL((rollup_pipe_kernel<FUNC_CT, false>),
+                           dim3(pipe_grid_blocks<FUNC_CT, false>(blocks, lds)),
                            dim3(BLOCK_THREADS), lds, stream, p, w);
     } else {
-      launch_rollup_t<FUNC_CT>(0, blocks, lds, p, w, stream);
+      launch_rollup_t<FUNC_CT>(0, std::min<uint32_t>(blocks, MAX_WAVE_BLOCKS),
+                               lds, p, w, stream);
     }
   } else {
     hipLaunchKernelGGL(rollup_huge_kernel<FUNC_CT>, dim3(blocks),
@@ -3596,14 +3791,17 @@ int vmgpu_rollup_exec(const vmgpu_plan* plan, uint64_t handle,
     KIO w = io;
     w.series_sel = b.wave_is_identity ? nullptr : b.d_wave_list;
     w.n_sel = b.n_wave;
-    uint32_t blocks = std::min<uint32_t>((b.n_wave + WAVES_PER_BLOCK - 1) / WAVES_PER_BLOCK,
-                                         MAX_WAVE_BLOCKS);
+    uint32_t need = (b.n_wave + WAVES_PER_BLOCK - 1) / WAVES_PER_BLOCK;
+    uint32_t blocks = std::min<uint32_t>(need, MAX_WAVE_BLOCKS);
     size_t lds = (size_t)WAVES_PER_BLOCK *
                  (vm_wave_slab_bytes(p.chunk_wave, use_pipe) +
                   vm_jbuf_bytes(p.jbuf_mode, p.jbuf_elems));
     /* software-pipelined register-staged variant for short series (the
-     * config-2 flagship shape); VMGPU_DISABLE_PIPE=1 A/Bs the wave kernel */
-    launch_rollup(use_pipe ? 3 : 0, blocks, lds, p, w);
+     * config-2 flagship shape); VMGPU_DISABLE_PIPE=1 A/Bs the wave kernel.
+     * The pipe launch sizes its own grid from the blocks needed
+     * (pipe_grid_blocks); VMGPU_PIPE_BLOCKS=<n> overrides that grid, read
+     * at every exec. */
+    launch_rollup(use_pipe ? 3 : 0, use_pipe ? need : blocks, lds, p, w);
   }
   if (b.n_block) {
     KIO w = io;
