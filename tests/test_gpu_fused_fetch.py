@@ -187,3 +187,56 @@ def test_packed_stream_matches_direct_batch():
     np.testing.assert_array_equal(out_p.view(np.int64), out_d.view(np.int64))
     b_packed.close()
     b_direct.close()
+
+
+def test_packed_batch_length_classes_match_direct_batch():
+    """A packed batch and a direct batch go through the same builder, so
+    they agree in every length class: series at the class edges (512 is the
+    wave kernel's cap, 4064 the block kernel's) and one inside each class.
+    The block kernel's LDS is sized from the longest block-class series of
+    the batch, which the packed path has to record like the direct one."""
+    rng = np.random.default_rng(78)
+    lens = [1, 240, 512, 513, 1000, 4064, 4065, 5000]
+    step = 15_000
+    ts_parts, vi_parts, offs = [], [], [0]
+    for n in lens:
+        t = START + np.cumsum(rng.integers(step - 500, step + 501, n)).astype(np.int64)
+        v = np.cumsum(rng.integers(0, 500, n)).astype(np.int64)
+        ts_parts.append(t)
+        vi_parts.append(v)
+        offs.append(offs[-1] + n)
+    ts = np.concatenate(ts_parts)
+    vi = np.concatenate(vi_parts)
+    vals = vi.astype(np.float64)
+    offsets = np.asarray(offs, dtype=np.uint64)
+    packed, n_blocks, sbs = oracle.pack_blocks(ts, vi, offsets)
+
+    # 100 points inside the span of the 240-sample series (about 3600 s)
+    start = START + 600_000
+    end = start + 100 * step
+
+    b_packed = SeriesBatch.from_packed(packed, n_blocks, sbs)
+    np.testing.assert_array_equal(b_packed.offsets, offsets)
+    b_direct = SeriesBatch(ts, vals, offsets)
+    for func in ("rate", "avg_over_time"):
+        plan = RollupPlan(func, start, end, step, window=300_000)
+        out_p, _, sc_p = b_packed.exec(plan)
+        out_d, _, sc_d = b_direct.exec(plan)
+        assert sc_p == sc_d, func
+        np.testing.assert_array_equal(out_p.view(np.int64),
+                                      out_d.view(np.int64), err_msg=func)
+    b_packed.close()
+    b_direct.close()
+
+    gids = (np.arange(len(lens)) % 3).astype(np.int32)
+    g_packed = SeriesBatch.from_packed(packed, n_blocks, sbs,
+                                       group_ids=gids, n_groups=3)
+    g_direct = SeriesBatch(ts, vals, offsets, group_ids=gids, n_groups=3)
+    plan = RollupPlan("rate", start, end, step, window=300_000, aggr="sum")
+    out_p, cnt_p, sc_p = g_packed.exec(plan)
+    out_d, cnt_d, sc_d = g_direct.exec(plan)
+    g_packed.close()
+    g_direct.close()
+    assert sc_p == sc_d
+    np.testing.assert_allclose(out_p, out_d, rtol=1e-9)
+    np.testing.assert_array_equal(cnt_p, cnt_d)

@@ -25,33 +25,8 @@
 #include <algorithm>
 #include <cstdio>
 
+#include "host_common.h"
 #include "../../include/vmgpu.h"
-
-namespace {
-
-int cset_err(char* errbuf, size_t len, const char* msg) {
-  if (errbuf && len) snprintf(errbuf, len, "%s", msg);
-  return 1;
-}
-
-int chip_err(char* errbuf, size_t len, const char* what, hipError_t e) {
-  if (errbuf && len) snprintf(errbuf, len, "%s: %s", what, hipGetErrorString(e));
-  return 2;
-}
-
-#define CHIP_TRY(expr, what)                                               \
-  do {                                                                     \
-    hipError_t _e = (expr);                                                \
-    if (_e != hipSuccess) return chip_err(errbuf, errbuf_len, what, _e);   \
-  } while (0)
-
-struct CDevBuf {
-  void* p = nullptr;
-  ~CDevBuf() { if (p) (void)hipFree(p); }
-  hipError_t alloc(size_t n) { return hipMalloc(&p, n ? n : 1); }
-};
-
-}  // namespace
 
 static __device__ __forceinline__ double c_nan() {
   return __longlong_as_double(0x7ff8000000000000LL);
@@ -309,7 +284,7 @@ int vmgpu_colagg(int32_t op, const double* values, uint32_t n_series,
                  double phi, double* out, double* out2,
                  double* values_out, char* errbuf, size_t errbuf_len) {
   if (!values || !group_rows || !group_offsets || n_groups == 0 || n_grid == 0)
-    return cset_err(errbuf, errbuf_len, "vmgpu: bad colagg args");
+    return vm_set_err(errbuf, errbuf_len, "vmgpu: bad colagg args");
   hipStream_t st = 0;
   size_t vbytes = (size_t)n_series * n_grid * 8;
   uint64_t n_rows = group_offsets[n_groups];
@@ -323,13 +298,13 @@ int vmgpu_colagg(int32_t op, const double* values, uint32_t n_series,
                         op == VMGPU_COLAGG_DISTINCT || op == VMGPU_COLAGG_IQR_BOUNDS);
   bool per_series = (op == VMGPU_COLAGG_SHARE || op == VMGPU_COLAGG_ZSCORE);
   size_t out_elems = (size_t)n_groups * n_grid;
-  CDevBuf dv, dvo, dgr, dgo, dout, dout2, dscr;
-  CHIP_TRY(dv.alloc(vbytes), "alloc colagg vals");
-  CHIP_TRY(hipMemcpyAsync(dv.p, values, vbytes, hipMemcpyHostToDevice, st), "ul vals");
-  CHIP_TRY(dgr.alloc((size_t)n_rows * 4), "alloc colagg rows");
-  CHIP_TRY(dgo.alloc((size_t)(n_groups + 1) * 8), "alloc colagg off");
-  CHIP_TRY(hipMemcpyAsync(dgr.p, group_rows, (size_t)n_rows * 4, hipMemcpyHostToDevice, st), "ul rows");
-  CHIP_TRY(hipMemcpyAsync(dgo.p, group_offsets, (size_t)(n_groups + 1) * 8, hipMemcpyHostToDevice, st), "ul off");
+  VmDevBuf dv, dvo, dgr, dgo, dout, dout2, dscr;
+  VM_HIP_TRY(dv.alloc(vbytes), "alloc colagg vals");
+  VM_HIP_TRY(hipMemcpyAsync(dv.p, values, vbytes, hipMemcpyHostToDevice, st), "ul vals");
+  VM_HIP_TRY(dgr.alloc((size_t)n_rows * 4), "alloc colagg rows");
+  VM_HIP_TRY(dgo.alloc((size_t)(n_groups + 1) * 8), "alloc colagg off");
+  VM_HIP_TRY(hipMemcpyAsync(dgr.p, group_rows, (size_t)n_rows * 4, hipMemcpyHostToDevice, st), "ul rows");
+  VM_HIP_TRY(hipMemcpyAsync(dgo.p, group_offsets, (size_t)(n_groups + 1) * 8, hipMemcpyHostToDevice, st), "ul off");
   uint32_t blocks = (uint32_t)std::min<uint64_t>((out_elems + 255) / 256, 2048);
   uint32_t scratch_slots = 0;
   if (needs_scratch) {
@@ -340,23 +315,23 @@ int vmgpu_colagg(int32_t op, const double* values, uint32_t n_series,
       scratch_slots = blocks * 256;
       sbytes = (size_t)scratch_slots * max_members * 8;
     }
-    CHIP_TRY(dscr.alloc(sbytes), "alloc colagg scratch");
+    VM_HIP_TRY(dscr.alloc(sbytes), "alloc colagg scratch");
   }
-  if (per_series) CHIP_TRY(dvo.alloc(vbytes), "alloc colagg vout");
-  if (out) CHIP_TRY(dout.alloc(out_elems * 8), "alloc colagg out");
-  if (out2) CHIP_TRY(dout2.alloc(out_elems * 8), "alloc colagg out2");
+  if (per_series) VM_HIP_TRY(dvo.alloc(vbytes), "alloc colagg vout");
+  if (out) VM_HIP_TRY(dout.alloc(out_elems * 8), "alloc colagg out");
+  if (out2) VM_HIP_TRY(dout2.alloc(out_elems * 8), "alloc colagg out2");
   hipLaunchKernelGGL(colagg_kernel, dim3(blocks), dim3(256), 0, st, op,
                      (const double*)dv.p, (double*)dvo.p,
                      (const uint32_t*)dgr.p, (const uint64_t*)dgo.p,
                      n_groups, n_grid, phi, (double*)dscr.p, scratch_slots,
                      max_members, (double*)dout.p, (double*)dout2.p);
-  if (out) CHIP_TRY(hipMemcpyAsync(out, dout.p, out_elems * 8, hipMemcpyDeviceToHost, st), "dl out");
-  if (out2) CHIP_TRY(hipMemcpyAsync(out2, dout2.p, out_elems * 8, hipMemcpyDeviceToHost, st), "dl out2");
+  if (out) VM_HIP_TRY(hipMemcpyAsync(out, dout.p, out_elems * 8, hipMemcpyDeviceToHost, st), "dl out");
+  if (out2) VM_HIP_TRY(hipMemcpyAsync(out2, dout2.p, out_elems * 8, hipMemcpyDeviceToHost, st), "dl out2");
   if (per_series && values_out)
-    CHIP_TRY(hipMemcpyAsync(values_out, dvo.p, vbytes, hipMemcpyDeviceToHost, st), "dl vout");
-  CHIP_TRY(hipStreamSynchronize(st), "sync colagg");
+    VM_HIP_TRY(hipMemcpyAsync(values_out, dvo.p, vbytes, hipMemcpyDeviceToHost, st), "dl vout");
+  VM_HIP_TRY(hipStreamSynchronize(st), "sync colagg");
   hipError_t kerr = hipGetLastError();
-  if (kerr != hipSuccess) return chip_err(errbuf, errbuf_len, "colagg kernel", kerr);
+  if (kerr != hipSuccess) return vm_hip_err(errbuf, errbuf_len, "colagg kernel", kerr);
   return 0;
 }
 
@@ -366,29 +341,29 @@ int vmgpu_colagg_filter(int32_t mode, const double* values,
                         uint32_t n_groups, uint8_t* flags,
                         char* errbuf, size_t errbuf_len) {
   if (!values || !group_of || !b1 || !b2 || !flags || n_series == 0)
-    return cset_err(errbuf, errbuf_len, "vmgpu: bad colagg filter args");
+    return vm_set_err(errbuf, errbuf_len, "vmgpu: bad colagg filter args");
   hipStream_t st = 0;
   size_t vbytes = (size_t)n_series * n_grid * 8;
   size_t bbytes = (size_t)n_groups * n_grid * 8;
-  CDevBuf dv, dgo, db1, db2, df;
-  CHIP_TRY(dv.alloc(vbytes), "alloc filt vals");
-  CHIP_TRY(dgo.alloc((size_t)n_series * 4), "alloc filt grp");
-  CHIP_TRY(db1.alloc(bbytes), "alloc filt b1");
-  CHIP_TRY(db2.alloc(bbytes), "alloc filt b2");
-  CHIP_TRY(df.alloc(n_series), "alloc filt flags");
-  CHIP_TRY(hipMemcpyAsync(dv.p, values, vbytes, hipMemcpyHostToDevice, st), "ul vals");
-  CHIP_TRY(hipMemcpyAsync(dgo.p, group_of, (size_t)n_series * 4, hipMemcpyHostToDevice, st), "ul grp");
-  CHIP_TRY(hipMemcpyAsync(db1.p, b1, bbytes, hipMemcpyHostToDevice, st), "ul b1");
-  CHIP_TRY(hipMemcpyAsync(db2.p, b2, bbytes, hipMemcpyHostToDevice, st), "ul b2");
+  VmDevBuf dv, dgo, db1, db2, df;
+  VM_HIP_TRY(dv.alloc(vbytes), "alloc filt vals");
+  VM_HIP_TRY(dgo.alloc((size_t)n_series * 4), "alloc filt grp");
+  VM_HIP_TRY(db1.alloc(bbytes), "alloc filt b1");
+  VM_HIP_TRY(db2.alloc(bbytes), "alloc filt b2");
+  VM_HIP_TRY(df.alloc(n_series), "alloc filt flags");
+  VM_HIP_TRY(hipMemcpyAsync(dv.p, values, vbytes, hipMemcpyHostToDevice, st), "ul vals");
+  VM_HIP_TRY(hipMemcpyAsync(dgo.p, group_of, (size_t)n_series * 4, hipMemcpyHostToDevice, st), "ul grp");
+  VM_HIP_TRY(hipMemcpyAsync(db1.p, b1, bbytes, hipMemcpyHostToDevice, st), "ul b1");
+  VM_HIP_TRY(hipMemcpyAsync(db2.p, b2, bbytes, hipMemcpyHostToDevice, st), "ul b2");
   uint32_t blocks = std::min<uint32_t>((n_series + 255) / 256, 2048);
   hipLaunchKernelGGL(colagg_filter_kernel, dim3(blocks), dim3(256), 0, st,
                      mode, (const double*)dv.p, (const int32_t*)dgo.p,
                      (const double*)db1.p, (const double*)db2.p,
                      n_series, n_grid, (uint8_t*)df.p);
-  CHIP_TRY(hipMemcpyAsync(flags, df.p, n_series, hipMemcpyDeviceToHost, st), "dl flags");
-  CHIP_TRY(hipStreamSynchronize(st), "sync filt");
+  VM_HIP_TRY(hipMemcpyAsync(flags, df.p, n_series, hipMemcpyDeviceToHost, st), "dl flags");
+  VM_HIP_TRY(hipStreamSynchronize(st), "sync filt");
   hipError_t kerr = hipGetLastError();
-  if (kerr != hipSuccess) return chip_err(errbuf, errbuf_len, "filt kernel", kerr);
+  if (kerr != hipSuccess) return vm_hip_err(errbuf, errbuf_len, "filt kernel", kerr);
   return 0;
 }
 

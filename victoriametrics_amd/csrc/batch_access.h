@@ -1,5 +1,6 @@
 /* Narrow internal window onto a resident batch for entry points that live
- * outside vmgpu.hip (Batch itself stays private there).  Same spirit as
+ * outside vmgpu.hip (hot.hip, cvot.hip, topk.hip; hstat.hip takes only the
+ * context lock from here).  Batch itself stays private.  Same spirit as
  * vm_ctx_stream (devalloc.h): the caller runs on the context stream and
  * holds the context lock for as long as it uses what it got here. */
 #ifndef VMGPU_BATCH_ACCESS_H
@@ -64,6 +65,11 @@ struct vm_batch_cols {
                               * NULL = identity */
   vm_hot_state* hot;
   vm_cvot_state* cvot;
+  /* resident output of the last vmgpu_rollup_exec (topk.hip selects from it
+   * and masks it in place): [last_rows x last_grid], NULL / 0 before one */
+  double* d_out;
+  uint32_t last_rows;
+  int32_t last_grid;
 };
 
 std::mutex& vm_ctx_mutex(void);

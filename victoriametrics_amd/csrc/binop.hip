@@ -27,27 +27,8 @@
 #include <cstdio>
 #include <vector>
 
+#include "host_common.h"
 #include "../../include/vmgpu.h"
-
-namespace {
-
-int bset_err(char* errbuf, size_t len, const char* msg) {
-  if (errbuf && len) snprintf(errbuf, len, "%s", msg);
-  return 1;
-}
-
-int bhip_err(char* errbuf, size_t len, const char* what, hipError_t e) {
-  if (errbuf && len) snprintf(errbuf, len, "%s: %s", what, hipGetErrorString(e));
-  return 2;
-}
-
-#define BHIP_TRY(expr, what)                                               \
-  do {                                                                     \
-    hipError_t _e = (expr);                                                \
-    if (_e != hipSuccess) return bhip_err(errbuf, errbuf_len, what, _e);   \
-  } while (0)
-
-}  // namespace
 
 static __device__ __forceinline__ double b_nan() {
   return __longlong_as_double(0x7ff8000000000000LL);
@@ -209,16 +190,6 @@ __global__ void binop_or_kernel(double* left_vals, double* right_vals,
   }
 }
 
-namespace {
-
-struct DevBuf {
-  void* p = nullptr;
-  ~DevBuf() { if (p) (void)hipFree(p); }
-  hipError_t alloc(size_t n) { return hipMalloc(&p, n ? n : 1); }
-};
-
-}  // namespace
-
 extern "C" {
 
 int vmgpu_binop_eval(int32_t op, int32_t is_bool, int32_t drop_nan_right,
@@ -231,27 +202,27 @@ int vmgpu_binop_eval(int32_t op, int32_t is_bool, int32_t drop_nan_right,
                      int32_t has_fill_right, double fill_right,
                      double* out, char* errbuf, size_t errbuf_len) {
   if (!left_vals || !right_vals || !out || n_pairs == 0 || n_grid == 0)
-    return bset_err(errbuf, errbuf_len, "vmgpu: bad binop args");
+    return vm_set_err(errbuf, errbuf_len, "vmgpu: bad binop args");
   hipStream_t st = 0;
   size_t lbytes = (size_t)n_left_rows * n_grid * 8;
   size_t rbytes = (size_t)n_right_rows * n_grid * 8;
   size_t obytes = (size_t)n_pairs * n_grid * 8;
-  DevBuf dl, dr, dli, dri, dout;
-  BHIP_TRY(dl.alloc(lbytes), "alloc binop left");
-  BHIP_TRY(dr.alloc(rbytes), "alloc binop right");
-  BHIP_TRY(dout.alloc(obytes), "alloc binop out");
-  BHIP_TRY(hipMemcpyAsync(dl.p, left_vals, lbytes, hipMemcpyHostToDevice, st), "ul left");
-  BHIP_TRY(hipMemcpyAsync(dr.p, right_vals, rbytes, hipMemcpyHostToDevice, st), "ul right");
+  VmDevBuf dl, dr, dli, dri, dout;
+  VM_HIP_TRY(dl.alloc(lbytes), "alloc binop left");
+  VM_HIP_TRY(dr.alloc(rbytes), "alloc binop right");
+  VM_HIP_TRY(dout.alloc(obytes), "alloc binop out");
+  VM_HIP_TRY(hipMemcpyAsync(dl.p, left_vals, lbytes, hipMemcpyHostToDevice, st), "ul left");
+  VM_HIP_TRY(hipMemcpyAsync(dr.p, right_vals, rbytes, hipMemcpyHostToDevice, st), "ul right");
   uint32_t* d_li = nullptr;
   uint32_t* d_ri = nullptr;
   if (left_idx) {
-    BHIP_TRY(dli.alloc((size_t)n_pairs * 4), "alloc left idx");
-    BHIP_TRY(hipMemcpyAsync(dli.p, left_idx, (size_t)n_pairs * 4, hipMemcpyHostToDevice, st), "ul left idx");
+    VM_HIP_TRY(dli.alloc((size_t)n_pairs * 4), "alloc left idx");
+    VM_HIP_TRY(hipMemcpyAsync(dli.p, left_idx, (size_t)n_pairs * 4, hipMemcpyHostToDevice, st), "ul left idx");
     d_li = (uint32_t*)dli.p;
   }
   if (right_idx) {
-    BHIP_TRY(dri.alloc((size_t)n_pairs * 4), "alloc right idx");
-    BHIP_TRY(hipMemcpyAsync(dri.p, right_idx, (size_t)n_pairs * 4, hipMemcpyHostToDevice, st), "ul right idx");
+    VM_HIP_TRY(dri.alloc((size_t)n_pairs * 4), "alloc right idx");
+    VM_HIP_TRY(hipMemcpyAsync(dri.p, right_idx, (size_t)n_pairs * 4, hipMemcpyHostToDevice, st), "ul right idx");
     d_ri = (uint32_t*)dri.p;
   }
   uint64_t total = (uint64_t)n_pairs * n_grid;
@@ -261,10 +232,10 @@ int vmgpu_binop_eval(int32_t op, int32_t is_bool, int32_t drop_nan_right,
                      (const double*)dr.p, d_ri, n_pairs, n_grid,
                      has_fill_left, fill_left, has_fill_right, fill_right,
                      (double*)dout.p);
-  BHIP_TRY(hipMemcpyAsync(out, dout.p, obytes, hipMemcpyDeviceToHost, st), "dl out");
-  BHIP_TRY(hipStreamSynchronize(st), "sync binop");
+  VM_HIP_TRY(hipMemcpyAsync(out, dout.p, obytes, hipMemcpyDeviceToHost, st), "dl out");
+  VM_HIP_TRY(hipStreamSynchronize(st), "sync binop");
   hipError_t kerr = hipGetLastError();
-  if (kerr != hipSuccess) return bhip_err(errbuf, errbuf_len, "binop kernel", kerr);
+  if (kerr != hipSuccess) return vm_hip_err(errbuf, errbuf_len, "binop kernel", kerr);
   return 0;
 }
 
@@ -276,32 +247,32 @@ int vmgpu_binop_mask(int32_t mode, double* left_vals, uint32_t n_left,
                      uint32_t n_grid, char* errbuf, size_t errbuf_len) {
   if (!left_vals || !left_group || !right_vals || !group_offsets || !group_rows ||
       n_left == 0 || n_grid == 0)
-    return bset_err(errbuf, errbuf_len, "vmgpu: bad binop mask args");
+    return vm_set_err(errbuf, errbuf_len, "vmgpu: bad binop mask args");
   hipStream_t st = 0;
   size_t lbytes = (size_t)n_left * n_grid * 8;
   size_t rbytes = (size_t)n_right * n_grid * 8;
   uint32_t n_rows = group_offsets[n_groups];
-  DevBuf dl, dr, dlg, dgo, dgr;
-  BHIP_TRY(dl.alloc(lbytes), "alloc mask left");
-  BHIP_TRY(dr.alloc(rbytes), "alloc mask right");
-  BHIP_TRY(dlg.alloc((size_t)n_left * 4), "alloc mask lgroup");
-  BHIP_TRY(dgo.alloc((size_t)(n_groups + 1) * 4), "alloc mask goff");
-  BHIP_TRY(dgr.alloc((size_t)n_rows * 4), "alloc mask grows");
-  BHIP_TRY(hipMemcpyAsync(dl.p, left_vals, lbytes, hipMemcpyHostToDevice, st), "ul mask left");
-  BHIP_TRY(hipMemcpyAsync(dr.p, right_vals, rbytes, hipMemcpyHostToDevice, st), "ul mask right");
-  BHIP_TRY(hipMemcpyAsync(dlg.p, left_group, (size_t)n_left * 4, hipMemcpyHostToDevice, st), "ul mask lg");
-  BHIP_TRY(hipMemcpyAsync(dgo.p, group_offsets, (size_t)(n_groups + 1) * 4, hipMemcpyHostToDevice, st), "ul mask go");
-  BHIP_TRY(hipMemcpyAsync(dgr.p, group_rows, (size_t)n_rows * 4, hipMemcpyHostToDevice, st), "ul mask gr");
+  VmDevBuf dl, dr, dlg, dgo, dgr;
+  VM_HIP_TRY(dl.alloc(lbytes), "alloc mask left");
+  VM_HIP_TRY(dr.alloc(rbytes), "alloc mask right");
+  VM_HIP_TRY(dlg.alloc((size_t)n_left * 4), "alloc mask lgroup");
+  VM_HIP_TRY(dgo.alloc((size_t)(n_groups + 1) * 4), "alloc mask goff");
+  VM_HIP_TRY(dgr.alloc((size_t)n_rows * 4), "alloc mask grows");
+  VM_HIP_TRY(hipMemcpyAsync(dl.p, left_vals, lbytes, hipMemcpyHostToDevice, st), "ul mask left");
+  VM_HIP_TRY(hipMemcpyAsync(dr.p, right_vals, rbytes, hipMemcpyHostToDevice, st), "ul mask right");
+  VM_HIP_TRY(hipMemcpyAsync(dlg.p, left_group, (size_t)n_left * 4, hipMemcpyHostToDevice, st), "ul mask lg");
+  VM_HIP_TRY(hipMemcpyAsync(dgo.p, group_offsets, (size_t)(n_groups + 1) * 4, hipMemcpyHostToDevice, st), "ul mask go");
+  VM_HIP_TRY(hipMemcpyAsync(dgr.p, group_rows, (size_t)n_rows * 4, hipMemcpyHostToDevice, st), "ul mask gr");
   uint64_t total = (uint64_t)n_left * n_grid;
   uint32_t blocks = (uint32_t)std::min<uint64_t>((total + 255) / 256, 4096);
   hipLaunchKernelGGL(binop_mask_kernel, dim3(blocks), dim3(256), 0, st,
                      mode, (double*)dl.p, (const uint32_t*)dlg.p, n_left,
                      (const double*)dr.p, (const uint32_t*)dgo.p,
                      (const uint32_t*)dgr.p, n_grid);
-  BHIP_TRY(hipMemcpyAsync(left_vals, dl.p, lbytes, hipMemcpyDeviceToHost, st), "dl mask left");
-  BHIP_TRY(hipStreamSynchronize(st), "sync mask");
+  VM_HIP_TRY(hipMemcpyAsync(left_vals, dl.p, lbytes, hipMemcpyDeviceToHost, st), "dl mask left");
+  VM_HIP_TRY(hipStreamSynchronize(st), "sync mask");
   hipError_t kerr = hipGetLastError();
-  if (kerr != hipSuccess) return bhip_err(errbuf, errbuf_len, "mask kernel", kerr);
+  if (kerr != hipSuccess) return vm_hip_err(errbuf, errbuf_len, "mask kernel", kerr);
   return 0;
 }
 
@@ -313,29 +284,29 @@ int vmgpu_binop_or(double* left_vals, uint32_t n_left,
                    uint64_t merge_len, uint32_t n_groups, uint32_t n_grid,
                    char* errbuf, size_t errbuf_len) {
   if (!left_vals || !right_vals || n_groups == 0 || n_grid == 0)
-    return bset_err(errbuf, errbuf_len, "vmgpu: bad binop or args");
+    return vm_set_err(errbuf, errbuf_len, "vmgpu: bad binop or args");
   hipStream_t st = 0;
   size_t lbytes = (size_t)n_left * n_grid * 8;
   size_t rbytes = (size_t)n_right * n_grid * 8;
   uint32_t nlr = lgroup_offsets[n_groups];
   uint32_t nrr = rgroup_offsets[n_groups];
-  DevBuf dl, dr, dlo, dlr, dro, drr, dcm, dmo;
-  BHIP_TRY(dl.alloc(lbytes), "alloc or left");
-  BHIP_TRY(dr.alloc(rbytes), "alloc or right");
-  BHIP_TRY(dlo.alloc((size_t)(n_groups + 1) * 4), "alloc or lo");
-  BHIP_TRY(dlr.alloc((size_t)nlr * 4), "alloc or lr");
-  BHIP_TRY(dro.alloc((size_t)(n_groups + 1) * 4), "alloc or ro");
-  BHIP_TRY(drr.alloc((size_t)nrr * 4), "alloc or rr");
-  BHIP_TRY(dcm.alloc(merge_len), "alloc or cm");
-  BHIP_TRY(dmo.alloc((size_t)n_groups * 8), "alloc or mo");
-  BHIP_TRY(hipMemcpyAsync(dl.p, left_vals, lbytes, hipMemcpyHostToDevice, st), "ul or l");
-  BHIP_TRY(hipMemcpyAsync(dr.p, right_vals, rbytes, hipMemcpyHostToDevice, st), "ul or r");
-  BHIP_TRY(hipMemcpyAsync(dlo.p, lgroup_offsets, (size_t)(n_groups + 1) * 4, hipMemcpyHostToDevice, st), "ul or lo");
-  BHIP_TRY(hipMemcpyAsync(dlr.p, lgroup_rows, (size_t)nlr * 4, hipMemcpyHostToDevice, st), "ul or lr");
-  BHIP_TRY(hipMemcpyAsync(dro.p, rgroup_offsets, (size_t)(n_groups + 1) * 4, hipMemcpyHostToDevice, st), "ul or ro");
-  BHIP_TRY(hipMemcpyAsync(drr.p, rgroup_rows, (size_t)nrr * 4, hipMemcpyHostToDevice, st), "ul or rr");
-  BHIP_TRY(hipMemcpyAsync(dcm.p, can_merge, merge_len, hipMemcpyHostToDevice, st), "ul or cm");
-  BHIP_TRY(hipMemcpyAsync(dmo.p, merge_offsets, (size_t)n_groups * 8, hipMemcpyHostToDevice, st), "ul or mo");
+  VmDevBuf dl, dr, dlo, dlr, dro, drr, dcm, dmo;
+  VM_HIP_TRY(dl.alloc(lbytes), "alloc or left");
+  VM_HIP_TRY(dr.alloc(rbytes), "alloc or right");
+  VM_HIP_TRY(dlo.alloc((size_t)(n_groups + 1) * 4), "alloc or lo");
+  VM_HIP_TRY(dlr.alloc((size_t)nlr * 4), "alloc or lr");
+  VM_HIP_TRY(dro.alloc((size_t)(n_groups + 1) * 4), "alloc or ro");
+  VM_HIP_TRY(drr.alloc((size_t)nrr * 4), "alloc or rr");
+  VM_HIP_TRY(dcm.alloc(merge_len), "alloc or cm");
+  VM_HIP_TRY(dmo.alloc((size_t)n_groups * 8), "alloc or mo");
+  VM_HIP_TRY(hipMemcpyAsync(dl.p, left_vals, lbytes, hipMemcpyHostToDevice, st), "ul or l");
+  VM_HIP_TRY(hipMemcpyAsync(dr.p, right_vals, rbytes, hipMemcpyHostToDevice, st), "ul or r");
+  VM_HIP_TRY(hipMemcpyAsync(dlo.p, lgroup_offsets, (size_t)(n_groups + 1) * 4, hipMemcpyHostToDevice, st), "ul or lo");
+  VM_HIP_TRY(hipMemcpyAsync(dlr.p, lgroup_rows, (size_t)nlr * 4, hipMemcpyHostToDevice, st), "ul or lr");
+  VM_HIP_TRY(hipMemcpyAsync(dro.p, rgroup_offsets, (size_t)(n_groups + 1) * 4, hipMemcpyHostToDevice, st), "ul or ro");
+  VM_HIP_TRY(hipMemcpyAsync(drr.p, rgroup_rows, (size_t)nrr * 4, hipMemcpyHostToDevice, st), "ul or rr");
+  VM_HIP_TRY(hipMemcpyAsync(dcm.p, can_merge, merge_len, hipMemcpyHostToDevice, st), "ul or cm");
+  VM_HIP_TRY(hipMemcpyAsync(dmo.p, merge_offsets, (size_t)n_groups * 8, hipMemcpyHostToDevice, st), "ul or mo");
   uint64_t total = (uint64_t)n_groups * n_grid;
   uint32_t blocks = (uint32_t)std::min<uint64_t>((total + 255) / 256, 4096);
   hipLaunchKernelGGL(binop_or_kernel, dim3(blocks), dim3(256), 0, st,
@@ -344,11 +315,11 @@ int vmgpu_binop_or(double* left_vals, uint32_t n_left,
                      (const uint32_t*)dro.p, (const uint32_t*)drr.p,
                      (const uint8_t*)dcm.p, (const uint64_t*)dmo.p,
                      n_groups, n_grid);
-  BHIP_TRY(hipMemcpyAsync(left_vals, dl.p, lbytes, hipMemcpyDeviceToHost, st), "dl or l");
-  BHIP_TRY(hipMemcpyAsync(right_vals, dr.p, rbytes, hipMemcpyDeviceToHost, st), "dl or r");
-  BHIP_TRY(hipStreamSynchronize(st), "sync or");
+  VM_HIP_TRY(hipMemcpyAsync(left_vals, dl.p, lbytes, hipMemcpyDeviceToHost, st), "dl or l");
+  VM_HIP_TRY(hipMemcpyAsync(right_vals, dr.p, rbytes, hipMemcpyDeviceToHost, st), "dl or r");
+  VM_HIP_TRY(hipStreamSynchronize(st), "sync or");
   hipError_t kerr = hipGetLastError();
-  if (kerr != hipSuccess) return bhip_err(errbuf, errbuf_len, "or kernel", kerr);
+  if (kerr != hipSuccess) return vm_hip_err(errbuf, errbuf_len, "or kernel", kerr);
   return 0;
 }
 

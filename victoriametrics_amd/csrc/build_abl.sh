@@ -6,11 +6,14 @@ cd "$(dirname "$0")"
 FLAGS="--offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off -fPIC"
 mkdir -p .abl
 
-# the same sources as build.sh: vmgpu.hip refers to every one of them
+# the same sources as build.sh: the library exports entry points from every
+# one of them, and all but binop, transform and aggrcol use vmgpu.hip's
+# context
 build_one() {
   name=$1
   shift
-  hipcc $FLAGS "$@" -shared vmgpu.hip decode.hip binop.hip transform.hip aggrcol.hip hot.hip cvot.hip -o ../libvmgpu_$name.so
+  hipcc $FLAGS "$@" -shared vmgpu.hip decode.hip binop.hip transform.hip aggrcol.hip hot.hip cvot.hip \
+    topk.hip hstat.hip -o ../libvmgpu_$name.so
 }
 
 build_one pipe_stage -DVMGPU_PIPE_ABL_STAGE &

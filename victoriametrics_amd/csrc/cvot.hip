@@ -431,21 +431,21 @@ int vmgpu_count_values_over_time_exec(uint64_t handle, int64_t start, int64_t en
                                       char* errbuf, size_t errbuf_len) {
   std::lock_guard<std::mutex> lock(vm_ctx_mutex());
   if (!vm_ctx_inited())
-    return hot_set_err(errbuf, errbuf_len, "vmgpu: not initialized");
+    return vm_set_err(errbuf, errbuf_len, "vmgpu: not initialized");
   vm_batch_cols b;
   if (vm_batch_cols_get(handle, &b) != 0)
-    return hot_set_err(errbuf, errbuf_len, "vmgpu: bad handle");
+    return vm_set_err(errbuf, errbuf_len, "vmgpu: bad handle");
   if (window <= 0)
-    return hot_set_err(errbuf, errbuf_len,
+    return vm_set_err(errbuf, errbuf_len,
                        "vmgpu: count_values_over_time needs an explicit window "
                        "(m[d] range selector)");
   if (step <= 0 || end < start)
-    return hot_set_err(errbuf, errbuf_len, "vmgpu: bad grid");
+    return vm_set_err(errbuf, errbuf_len, "vmgpu: bad grid");
   int64_t n_grid64 = 1 + (end - start) / step;
   if (n_grid64 > (int64_t)1 << 30)
-    return hot_set_err(errbuf, errbuf_len, "vmgpu: grid too large");
+    return vm_set_err(errbuf, errbuf_len, "vmgpu: grid too large");
   if (b.n_samples >= CVOT_ROW_NONE)
-    return hot_set_err(errbuf, errbuf_len,
+    return vm_set_err(errbuf, errbuf_len,
                        "vmgpu: batch too large for count_values_over_time");
   HotParams p;
   p.start = start;
@@ -465,30 +465,30 @@ int vmgpu_count_values_over_time_exec(uint64_t handle, int64_t start, int64_t en
     /* scratch is sized by the batch, so each piece is allocated once */
     size_t cap = 0;
     if (!h.d_local_row)
-      HOT_TRY(hot_reserve(&h.d_local_row, &cap, (size_t)b.n_samples * 4 + 16),
+      VM_HIP_TRY(hot_reserve(&h.d_local_row, &cap, (size_t)b.n_samples * 4 + 16),
               "alloc local rows");
     if (!h.d_row_keys)
-      HOT_TRY(hot_reserve(&h.d_row_keys, &cap, (size_t)b.n_samples * 8 + 16),
+      VM_HIP_TRY(hot_reserve(&h.d_row_keys, &cap, (size_t)b.n_samples * 8 + 16),
               "alloc row keys");
     if (!h.d_row_counts)
-      HOT_TRY(hot_reserve(&h.d_row_counts, &cap, (size_t)ns * 4 + 16),
+      VM_HIP_TRY(hot_reserve(&h.d_row_counts, &cap, (size_t)ns * 4 + 16),
               "alloc row counts");
     if (!h.d_row_start)
-      HOT_TRY(hot_reserve(&h.d_row_start, &cap, ((size_t)ns + 1) * 8), "alloc row start");
+      VM_HIP_TRY(hot_reserve(&h.d_row_start, &cap, ((size_t)ns + 1) * 8), "alloc row start");
     if (!h.d_long_list)
-      HOT_TRY(hot_reserve(&h.d_long_list, &cap, (size_t)ns * 4 + 16),
+      VM_HIP_TRY(hot_reserve(&h.d_long_list, &cap, (size_t)ns * 4 + 16),
               "alloc long-series list");
     if (!h.d_small)
-      HOT_TRY(hot_reserve(&h.d_small, &cap, 16), "alloc counters");
+      VM_HIP_TRY(hot_reserve(&h.d_small, &cap, 16), "alloc counters");
   }
-  HOT_TRY(hipMemsetAsync(h.d_small, 0, 16, st), "zero counters");
+  VM_HIP_TRY(hipMemsetAsync(h.d_small, 0, 16, st), "zero counters");
 
   const uint32_t blocks = std::max<uint32_t>(1, std::min<uint32_t>(
       (ns + HOT_WAVES_PER_BLOCK - 1) / HOT_WAVES_PER_BLOCK, HOT_MAX_BLOCKS));
   const uint32_t long_blocks =
       std::max<uint32_t>(1, std::min<uint32_t>(ns, CVOT_LONG_BLOCKS));
 
-  HOT_TRY(hipEventRecord(ev_start, st), "event start");
+  VM_HIP_TRY(hipEventRecord(ev_start, st), "event start");
   hipLaunchKernelGGL(cvot_mark_kernel, dim3(blocks), dim3(HOT_BLOCK_THREADS), 0, st,
                      p, b.d_ts, b.d_vals, b.d_offsets, ns, h.d_local_row,
                      h.d_row_keys, h.d_row_counts, h.d_long_list, h.d_small);
@@ -500,17 +500,17 @@ int vmgpu_count_values_over_time_exec(uint64_t handle, int64_t start, int64_t en
   /* the output size is data-dependent: the host learns n_rows here */
   uint64_t n_rows = 0;
   unsigned long long scanned_h = 0;
-  HOT_TRY(hipMemcpyAsync(&n_rows, h.d_row_start + ns, 8, hipMemcpyDeviceToHost, st),
+  VM_HIP_TRY(hipMemcpyAsync(&n_rows, h.d_row_start + ns, 8, hipMemcpyDeviceToHost, st),
           "download n_rows");
-  HOT_TRY(hipMemcpyAsync(&scanned_h, h.d_small, 8, hipMemcpyDeviceToHost, st),
+  VM_HIP_TRY(hipMemcpyAsync(&scanned_h, h.d_small, 8, hipMemcpyDeviceToHost, st),
           "download scanned");
-  HOT_TRY(hipStreamSynchronize(st), "sync mark");
+  VM_HIP_TRY(hipStreamSynchronize(st), "sync mark");
   {
     hipError_t kerr = hipGetLastError();
-    if (kerr != hipSuccess) return hot_hip_err(errbuf, errbuf_len, "mark kernel", kerr);
+    if (kerr != hipSuccess) return vm_hip_err(errbuf, errbuf_len, "mark kernel", kerr);
   }
   if (n_rows > b.n_samples)
-    return hot_set_err(errbuf, errbuf_len, "vmgpu: inconsistent row count");
+    return vm_set_err(errbuf, errbuf_len, "vmgpu: inconsistent row count");
   if (max_rows && n_rows > max_rows) {
     if (errbuf && errbuf_len)
       snprintf(errbuf, errbuf_len,
@@ -523,22 +523,22 @@ int vmgpu_count_values_over_time_exec(uint64_t handle, int64_t start, int64_t en
   h.n_rows = n_rows;
   h.n_grid = p.n_grid;
   if (n_rows) {
-    HOT_TRY(hot_reserve(&h.d_out, &h.out_cap, (size_t)n_rows * p.n_grid * 8),
+    VM_HIP_TRY(hot_reserve(&h.d_out, &h.out_cap, (size_t)n_rows * p.n_grid * 8),
             "alloc count_values rows");
-    HOT_TRY(hot_reserve(&h.d_row_series, &h.row_series_cap, (size_t)n_rows * 4),
+    VM_HIP_TRY(hot_reserve(&h.d_row_series, &h.row_series_cap, (size_t)n_rows * 4),
             "alloc row series");
-    HOT_TRY(hot_reserve(&h.d_row_value, &h.row_value_cap, (size_t)n_rows * 8),
+    VM_HIP_TRY(hot_reserve(&h.d_row_value, &h.row_value_cap, (size_t)n_rows * 8),
             "alloc row values");
     hipLaunchKernelGGL(cvot_count_kernel, dim3(blocks), dim3(HOT_BLOCK_THREADS), 0, st,
                        p, b.d_ts, h.d_local_row, b.d_offsets, h.d_row_keys,
                        h.d_row_start, ns, h.d_out, h.d_row_series,
                        h.d_row_value);
   }
-  HOT_TRY(hipEventRecord(ev_stop, st), "event stop");
-  HOT_TRY(hipStreamSynchronize(st), "sync count");
-  HOT_TRY(hipGetLastError(), "count kernel");
+  VM_HIP_TRY(hipEventRecord(ev_stop, st), "event stop");
+  VM_HIP_TRY(hipStreamSynchronize(st), "sync count");
+  VM_HIP_TRY(hipGetLastError(), "count kernel");
   float ms = 0;
-  HOT_TRY(hipEventElapsedTime(&ms, ev_start, ev_stop), "event elapsed");
+  VM_HIP_TRY(hipEventElapsedTime(&ms, ev_start, ev_stop), "event elapsed");
   vm_ctx_set_last_kernel_ms((double)ms);
   h.valid = true;
   if (out_n_rows) *out_n_rows = n_rows;
@@ -551,31 +551,31 @@ int vmgpu_count_values_over_time_fetch(uint64_t handle, uint32_t* row_series,
                                        char* errbuf, size_t errbuf_len) {
   std::lock_guard<std::mutex> lock(vm_ctx_mutex());
   if (!vm_ctx_inited())
-    return hot_set_err(errbuf, errbuf_len, "vmgpu: not initialized");
+    return vm_set_err(errbuf, errbuf_len, "vmgpu: not initialized");
   vm_batch_cols b;
   if (vm_batch_cols_get(handle, &b) != 0)
-    return hot_set_err(errbuf, errbuf_len, "vmgpu: bad handle");
+    return vm_set_err(errbuf, errbuf_len, "vmgpu: bad handle");
   const vm_cvot_state& h = *b.cvot;
   if (!h.valid)
-    return hot_set_err(errbuf, errbuf_len,
+    return vm_set_err(errbuf, errbuf_len,
                        "vmgpu: no count_values_over_time result on this batch");
   if (h.n_rows == 0) return 0;
   hipStream_t st = vm_ctx_stream();
   if (row_series)
-    HOT_TRY(hipMemcpyAsync(row_series, h.d_row_series, h.n_rows * 4,
+    VM_HIP_TRY(hipMemcpyAsync(row_series, h.d_row_series, h.n_rows * 4,
                            hipMemcpyDeviceToHost, st), "download row series");
   if (row_value)
-    HOT_TRY(hipMemcpyAsync(row_value, h.d_row_value, h.n_rows * 8,
+    VM_HIP_TRY(hipMemcpyAsync(row_value, h.d_row_value, h.n_rows * 8,
                            hipMemcpyDeviceToHost, st), "download row values");
   if (out)
-    HOT_TRY(hipMemcpyAsync(out, h.d_out, (size_t)h.n_rows * h.n_grid * 8,
+    VM_HIP_TRY(hipMemcpyAsync(out, h.d_out, (size_t)h.n_rows * h.n_grid * 8,
                            hipMemcpyDeviceToHost, st), "download count_values rows");
-  HOT_TRY(hipStreamSynchronize(st), "sync fetch");
+  VM_HIP_TRY(hipStreamSynchronize(st), "sync fetch");
   if (row_series && b.perm)
     for (uint64_t i = 0; i < h.n_rows; i++) {
       uint32_t phys = row_series[i];
       if (phys >= b.n_series)
-        return hot_set_err(errbuf, errbuf_len, "vmgpu: corrupt row series");
+        return vm_set_err(errbuf, errbuf_len, "vmgpu: corrupt row series");
       row_series[i] = b.perm[phys];
     }
   return 0;

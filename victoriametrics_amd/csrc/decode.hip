@@ -27,7 +27,7 @@
  *            bit-identical to the CPU path.
  */
 #include <hip/hip_runtime.h>
-#include "devalloc.h"
+#include "host_common.h"
 #include <algorithm>
 #include <cstdio>
 #include <cstring>
@@ -41,26 +41,6 @@
 #define DMAX_ROWS 8192          /* maxRowsPerBlock, lib/storage/block.go:14 */
 #define DMAX_PAYLOAD (DMAX_ROWS * 10 + 16)
 #define DGRID 1024              /* workgroups; each owns a scratch column */
-
-namespace {
-
-int dset_err(char* errbuf, size_t len, const char* msg) {
-  if (errbuf && len) snprintf(errbuf, len, "%s", msg);
-  return 1;
-}
-
-int dhip_err(char* errbuf, size_t len, const char* what, hipError_t e) {
-  if (errbuf && len) snprintf(errbuf, len, "%s: %s", what, hipGetErrorString(e));
-  return 2;
-}
-
-#define DHIP_TRY(expr, what)                                               \
-  do {                                                                     \
-    hipError_t _e = (expr);                                                \
-    if (_e != hipSuccess) return dhip_err(errbuf, errbuf_len, what, _e);   \
-  } while (0)
-
-}  // namespace
 
 /* decimal special values (lib/decimal/decimal.go:403-419) */
 #define D_VINF_POS 0x7fffffffffffffffLL
@@ -337,44 +317,39 @@ int vmgpu_decode_blocks(const uint8_t* payload, uint64_t payload_len,
                         int64_t* out_ts, double* out_vals,
                         char* errbuf, size_t errbuf_len) {
   if (!payload || !blocks || !out_ts || !out_vals || n_blocks == 0)
-    return dset_err(errbuf, errbuf_len, "vmgpu: bad args");
+    return vm_set_err(errbuf, errbuf_len, "vmgpu: bad args");
   hipStream_t st = vm_ctx_stream();
-  uint8_t* d_payload = nullptr;
-  vmgpu_block_desc* d_blocks = nullptr;
-  long long* d_scratch = nullptr;
-  int64_t* d_ts = nullptr;
-  double* d_vals = nullptr;
-  int* d_err = nullptr;
-  DHIP_TRY(vm_dev_malloc(&d_payload, payload_len ? payload_len : 1), "alloc payload");
-  DHIP_TRY(vm_dev_malloc(&d_blocks, (size_t)n_blocks * sizeof(vmgpu_block_desc)), "alloc descs");
-  DHIP_TRY(vm_dev_malloc(&d_scratch, (size_t)DGRID * DMAX_ROWS * 8), "alloc scratch");
-  DHIP_TRY(vm_dev_malloc(&d_ts, (size_t)total_rows * 8), "alloc ts");
-  DHIP_TRY(vm_dev_malloc(&d_vals, (size_t)total_rows * 8), "alloc vals");
-  DHIP_TRY(vm_dev_malloc(&d_err, 4), "alloc err");
-  DHIP_TRY(hipMemcpyAsync(d_payload, payload, payload_len, hipMemcpyHostToDevice, st), "ul payload");
-  DHIP_TRY(hipMemcpyAsync(d_blocks, blocks, (size_t)n_blocks * sizeof(vmgpu_block_desc),
-                          hipMemcpyHostToDevice, st), "ul descs");
-  DHIP_TRY(hipMemsetAsync(d_err, 0, 4, st), "zero err");
+  VmPoolBuf<uint8_t> d_payload;
+  VmPoolBuf<vmgpu_block_desc> d_blocks;
+  VmPoolBuf<long long> d_scratch;
+  VmPoolBuf<int64_t> d_ts;
+  VmPoolBuf<double> d_vals;
+  VmPoolBuf<int> d_err;
+  VM_HIP_TRY(d_payload.alloc(payload_len ? payload_len : 1), "alloc payload");
+  VM_HIP_TRY(d_blocks.alloc((size_t)n_blocks * sizeof(vmgpu_block_desc)), "alloc descs");
+  VM_HIP_TRY(d_scratch.alloc((size_t)DGRID * DMAX_ROWS * 8), "alloc scratch");
+  VM_HIP_TRY(d_ts.alloc((size_t)total_rows * 8), "alloc ts");
+  VM_HIP_TRY(d_vals.alloc((size_t)total_rows * 8), "alloc vals");
+  VM_HIP_TRY(d_err.alloc(4), "alloc err");
+  VM_HIP_TRY(hipMemcpyAsync(d_payload.p, payload, payload_len, hipMemcpyHostToDevice, st), "ul payload");
+  VM_HIP_TRY(hipMemcpyAsync(d_blocks.p, blocks, (size_t)n_blocks * sizeof(vmgpu_block_desc),
+                            hipMemcpyHostToDevice, st), "ul descs");
+  VM_HIP_TRY(hipMemsetAsync(d_err.p, 0, 4, st), "zero err");
   uint32_t grid = std::min<uint32_t>(n_blocks, DGRID);
   hipLaunchKernelGGL(decode_blocks_kernel, dim3(grid), dim3(DBLOCK), 0, st,
-                     d_payload, d_blocks, n_blocks, d_scratch, d_ts, d_vals, d_err);
+                     d_payload.p, d_blocks.p, n_blocks, d_scratch.p, d_ts.p,
+                     d_vals.p, d_err.p);
   int err_h = 0;
-  DHIP_TRY(hipMemcpyAsync(&err_h, d_err, 4, hipMemcpyDeviceToHost, st), "dl err");
-  DHIP_TRY(hipMemcpyAsync(out_ts, d_ts, (size_t)total_rows * 8, hipMemcpyDeviceToHost, st), "dl ts");
-  DHIP_TRY(hipMemcpyAsync(out_vals, d_vals, (size_t)total_rows * 8, hipMemcpyDeviceToHost, st), "dl vals");
-  DHIP_TRY(hipStreamSynchronize(st), "sync");
+  VM_HIP_TRY(hipMemcpyAsync(&err_h, d_err.p, 4, hipMemcpyDeviceToHost, st), "dl err");
+  VM_HIP_TRY(hipMemcpyAsync(out_ts, d_ts.p, (size_t)total_rows * 8, hipMemcpyDeviceToHost, st), "dl ts");
+  VM_HIP_TRY(hipMemcpyAsync(out_vals, d_vals.p, (size_t)total_rows * 8, hipMemcpyDeviceToHost, st), "dl vals");
+  VM_HIP_TRY(hipStreamSynchronize(st), "sync");
   hipError_t kerr = hipGetLastError();
-  (void)vm_dev_free(d_payload);
-  (void)vm_dev_free(d_blocks);
-  (void)vm_dev_free(d_scratch);
-  (void)vm_dev_free(d_ts);
-  (void)vm_dev_free(d_vals);
-  (void)vm_dev_free(d_err);
-  if (kerr != hipSuccess) return dhip_err(errbuf, errbuf_len, "decode kernel", kerr);
+  if (kerr != hipSuccess) return vm_hip_err(errbuf, errbuf_len, "decode kernel", kerr);
   if (err_h != 0) {
     char msg[64];
     snprintf(msg, sizeof(msg), "vmgpu: block decode error %d", err_h);
-    return dset_err(errbuf, errbuf_len, msg);
+    return vm_set_err(errbuf, errbuf_len, msg);
   }
   return 0;
 }
@@ -645,7 +620,7 @@ int vmgpu_merge_blocks(const int64_t* ts, const double* vals,
                        char* errbuf, size_t errbuf_len) {
   if (!ts || !vals || !block_offsets || !series_block_start || !out_ts ||
       !out_vals || !out_offsets || !out_counts || n_series == 0)
-    return dset_err(errbuf, errbuf_len, "vmgpu: bad args");
+    return vm_set_err(errbuf, errbuf_len, "vmgpu: bad args");
   hipStream_t st = vm_ctx_stream();
   uint64_t total = block_offsets[n_blocks];
   /* capacity offsets = pre-merge block extents per series */
@@ -656,65 +631,58 @@ int vmgpu_merge_blocks(const int64_t* ts, const double* vals,
     uint64_t hi = block_offsets[series_block_start[s + 1]];
     cap_off[s + 1] = cap_off[s] + (hi - lo);
   }
-  int64_t* d_ts = nullptr;
-  double* d_vals = nullptr;
-  uint64_t* d_boff = nullptr;
-  uint32_t* d_sbs = nullptr;
-  uint64_t* d_ooff = nullptr;
-  int64_t* d_ots = nullptr;
-  double* d_ovals = nullptr;
-  uint64_t* d_ocnt = nullptr;
-  int* d_err = nullptr;
-  DHIP_TRY(vm_dev_malloc(&d_ts, total * 8), "alloc ts");
-  DHIP_TRY(vm_dev_malloc(&d_vals, total * 8), "alloc vals");
-  DHIP_TRY(vm_dev_malloc(&d_boff, (size_t)(n_blocks + 1) * 8), "alloc boff");
-  DHIP_TRY(vm_dev_malloc(&d_sbs, (size_t)(n_series + 1) * 4), "alloc sbs");
-  DHIP_TRY(vm_dev_malloc(&d_ooff, (size_t)(n_series + 1) * 8), "alloc ooff");
+  VmPoolBuf<int64_t> d_ts, d_ots;
+  VmPoolBuf<double> d_vals, d_ovals;
+  VmPoolBuf<uint64_t> d_boff, d_ooff, d_ocnt;
+  VmPoolBuf<uint32_t> d_sbs;
+  VmPoolBuf<int> d_err;
+  VM_HIP_TRY(d_ts.alloc(total * 8), "alloc ts");
+  VM_HIP_TRY(d_vals.alloc(total * 8), "alloc vals");
+  VM_HIP_TRY(d_boff.alloc((size_t)(n_blocks + 1) * 8), "alloc boff");
+  VM_HIP_TRY(d_sbs.alloc((size_t)(n_series + 1) * 4), "alloc sbs");
+  VM_HIP_TRY(d_ooff.alloc((size_t)(n_series + 1) * 8), "alloc ooff");
   /* +16 B slack for the pipe kernel's clamped tail pair load */
-  DHIP_TRY(vm_dev_malloc(&d_ots, cap_off[n_series] * 8 + 16), "alloc out ts");
-  DHIP_TRY(vm_dev_malloc(&d_ovals, cap_off[n_series] * 8 + 16), "alloc out vals");
-  DHIP_TRY(vm_dev_malloc(&d_ocnt, (size_t)n_series * 8), "alloc out counts");
-  DHIP_TRY(vm_dev_malloc(&d_err, 4), "alloc err");
-  DHIP_TRY(hipMemcpyAsync(d_ts, ts, total * 8, hipMemcpyHostToDevice, st), "ul ts");
-  DHIP_TRY(hipMemcpyAsync(d_vals, vals, total * 8, hipMemcpyHostToDevice, st), "ul vals");
-  DHIP_TRY(hipMemcpyAsync(d_boff, block_offsets, (size_t)(n_blocks + 1) * 8, hipMemcpyHostToDevice, st), "ul boff");
-  DHIP_TRY(hipMemcpyAsync(d_sbs, series_block_start, (size_t)(n_series + 1) * 4, hipMemcpyHostToDevice, st), "ul sbs");
-  DHIP_TRY(hipMemcpyAsync(d_ooff, cap_off.data(), (size_t)(n_series + 1) * 8, hipMemcpyHostToDevice, st), "ul ooff");
-  DHIP_TRY(hipMemsetAsync(d_err, 0, 4, st), "zero err");
+  VM_HIP_TRY(d_ots.alloc(cap_off[n_series] * 8 + 16), "alloc out ts");
+  VM_HIP_TRY(d_ovals.alloc(cap_off[n_series] * 8 + 16), "alloc out vals");
+  VM_HIP_TRY(d_ocnt.alloc((size_t)n_series * 8), "alloc out counts");
+  VM_HIP_TRY(d_err.alloc(4), "alloc err");
+  VM_HIP_TRY(hipMemcpyAsync(d_ts.p, ts, total * 8, hipMemcpyHostToDevice, st), "ul ts");
+  VM_HIP_TRY(hipMemcpyAsync(d_vals.p, vals, total * 8, hipMemcpyHostToDevice, st), "ul vals");
+  VM_HIP_TRY(hipMemcpyAsync(d_boff.p, block_offsets, (size_t)(n_blocks + 1) * 8, hipMemcpyHostToDevice, st), "ul boff");
+  VM_HIP_TRY(hipMemcpyAsync(d_sbs.p, series_block_start, (size_t)(n_series + 1) * 4, hipMemcpyHostToDevice, st), "ul sbs");
+  VM_HIP_TRY(hipMemcpyAsync(d_ooff.p, cap_off.data(), (size_t)(n_series + 1) * 8, hipMemcpyHostToDevice, st), "ul ooff");
+  VM_HIP_TRY(hipMemsetAsync(d_err.p, 0, 4, st), "zero err");
   uint32_t grid = std::min<uint32_t>((n_series + 3) / 4, 2048);
   hipLaunchKernelGGL(merge_blocks_kernel, dim3(grid), dim3(DBLOCK), 0, st,
-                     d_ts, d_vals, d_boff, d_sbs, d_ooff, n_series,
-                     dedup_interval, d_ots, d_ovals, d_ocnt, d_err);
+                     d_ts.p, d_vals.p, d_boff.p, d_sbs.p, d_ooff.p, n_series,
+                     dedup_interval, d_ots.p, d_ovals.p, d_ocnt.p, d_err.p);
   std::vector<uint64_t> counts(n_series);
   int err_h = 0;
-  DHIP_TRY(hipMemcpyAsync(counts.data(), d_ocnt, (size_t)n_series * 8, hipMemcpyDeviceToHost, st), "dl counts");
-  DHIP_TRY(hipMemcpyAsync(&err_h, d_err, 4, hipMemcpyDeviceToHost, st), "dl err");
+  VM_HIP_TRY(hipMemcpyAsync(counts.data(), d_ocnt.p, (size_t)n_series * 8, hipMemcpyDeviceToHost, st), "dl counts");
+  VM_HIP_TRY(hipMemcpyAsync(&err_h, d_err.p, 4, hipMemcpyDeviceToHost, st), "dl err");
   /* compact download: per series, copy the merged prefix */
-  DHIP_TRY(hipStreamSynchronize(st), "sync");
+  VM_HIP_TRY(hipStreamSynchronize(st), "sync");
   hipError_t kerr = hipGetLastError();
   if (kerr == hipSuccess && err_h == 0) {
     uint64_t w = 0;
     out_offsets[0] = 0;
     for (uint32_t s = 0; s < n_series; s++) {
       uint64_t n = counts[s];
-      DHIP_TRY(hipMemcpyAsync(out_ts + w, d_ots + cap_off[s], n * 8,
-                              hipMemcpyDeviceToHost, st), "dl merged ts");
-      DHIP_TRY(hipMemcpyAsync(out_vals + w, d_ovals + cap_off[s], n * 8,
-                              hipMemcpyDeviceToHost, st), "dl merged vals");
+      VM_HIP_TRY(hipMemcpyAsync(out_ts + w, d_ots.p + cap_off[s], n * 8,
+                                hipMemcpyDeviceToHost, st), "dl merged ts");
+      VM_HIP_TRY(hipMemcpyAsync(out_vals + w, d_ovals.p + cap_off[s], n * 8,
+                                hipMemcpyDeviceToHost, st), "dl merged vals");
       w += n;
       out_offsets[s + 1] = w;
       out_counts[s] = n;
     }
-    DHIP_TRY(hipStreamSynchronize(st), "sync dl");
+    VM_HIP_TRY(hipStreamSynchronize(st), "sync dl");
   }
-  (void)vm_dev_free(d_ts); (void)vm_dev_free(d_vals); (void)vm_dev_free(d_boff);
-  (void)vm_dev_free(d_sbs); (void)vm_dev_free(d_ooff); (void)vm_dev_free(d_ots);
-  (void)vm_dev_free(d_ovals); (void)vm_dev_free(d_ocnt); (void)vm_dev_free(d_err);
-  if (kerr != hipSuccess) return dhip_err(errbuf, errbuf_len, "merge kernel", kerr);
+  if (kerr != hipSuccess) return vm_hip_err(errbuf, errbuf_len, "merge kernel", kerr);
   if (err_h != 0) {
     char msg[64];
     snprintf(msg, sizeof(msg), "vmgpu: merge error %d", err_h);
-    return dset_err(errbuf, errbuf_len, msg);
+    return vm_set_err(errbuf, errbuf_len, msg);
   }
   return 0;
 }
@@ -760,7 +728,7 @@ extern "C" int vmdec_decode_merge_device(
     char* errbuf, size_t errbuf_len) {
   if (!payload || !blocks || !series_block_start || !out_d_ts || !out_d_vals ||
       !h_final_offsets || n_blocks == 0 || n_series == 0)
-    return dset_err(errbuf, errbuf_len, "vmgpu: bad fused decode args");
+    return vm_set_err(errbuf, errbuf_len, "vmgpu: bad fused decode args");
   /* host-side offsets for the merge: block b rows at [out_off, out_off+rows) */
   std::vector<uint64_t> boff(n_blocks + 1);
   for (uint32_t b = 0; b < n_blocks; b++) boff[b] = blocks[b].out_off;
@@ -773,106 +741,79 @@ extern "C" int vmdec_decode_merge_device(
     cap_off[s + 1] = cap_off[s] + (hi - lo);
   }
 
-  uint8_t* d_payload = nullptr;
-  vmgpu_block_desc* d_blocks = nullptr;
-  long long* d_scratch = nullptr;
-  int64_t* d_raw_ts = nullptr;
-  double* d_raw_vals = nullptr;
-  uint64_t* d_boff = nullptr;
-  uint32_t* d_sbs = nullptr;
-  uint64_t* d_capoff = nullptr;
-  int64_t* d_mts = nullptr;
-  double* d_mvals = nullptr;
-  uint64_t* d_cnt = nullptr;
-  uint64_t* d_finaloff = nullptr;
-  int* d_err = nullptr;
-  int64_t* d_fts = nullptr;
-  double* d_fvals = nullptr;
-  int rc = 0;
-  hipError_t kerr = hipSuccess;
+  VmPoolBuf<uint8_t> d_payload;
+  VmPoolBuf<vmgpu_block_desc> d_blocks;
+  VmPoolBuf<long long> d_scratch;
+  VmPoolBuf<int64_t> d_raw_ts, d_mts, d_fts;
+  VmPoolBuf<double> d_raw_vals, d_mvals, d_fvals;
+  VmPoolBuf<uint64_t> d_boff, d_capoff, d_cnt, d_finaloff;
+  VmPoolBuf<uint32_t> d_sbs;
+  VmPoolBuf<int> d_err;
   std::vector<uint64_t> counts(n_series);
   int err_h = 0;
-  uint32_t grid = 0, mgrid = 0;
 
-#define FDM_TRY(expr, what)                                                  \
-  do {                                                                       \
-    hipError_t _e = (expr);                                                  \
-    if (_e != hipSuccess) { rc = dhip_err(errbuf, errbuf_len, what, _e);     \
-      goto cleanup; }                                                        \
-  } while (0)
-
-  FDM_TRY(vm_dev_malloc(&d_payload, payload_len ? payload_len : 1), "alloc payload");
-  FDM_TRY(vm_dev_malloc(&d_blocks, (size_t)n_blocks * sizeof(vmgpu_block_desc)), "alloc descs");
-  FDM_TRY(vm_dev_malloc(&d_scratch, (size_t)DGRID * DMAX_ROWS * 8), "alloc scratch");
-  FDM_TRY(vm_dev_malloc(&d_raw_ts, (size_t)total_rows * 8), "alloc raw ts");
-  FDM_TRY(vm_dev_malloc(&d_raw_vals, (size_t)total_rows * 8), "alloc raw vals");
-  FDM_TRY(vm_dev_malloc(&d_err, 4), "alloc err");
-  FDM_TRY(hipMemcpyAsync(d_payload, payload, payload_len ? payload_len : 1,
-                         hipMemcpyHostToDevice, st), "ul payload");
-  FDM_TRY(hipMemcpyAsync(d_blocks, blocks, (size_t)n_blocks * sizeof(vmgpu_block_desc),
-                         hipMemcpyHostToDevice, st), "ul descs");
-  FDM_TRY(hipMemsetAsync(d_err, 0, 4, st), "zero err");
-  grid = std::min<uint32_t>(n_blocks, DGRID);
+  VM_HIP_TRY(d_payload.alloc(payload_len ? payload_len : 1), "alloc payload");
+  VM_HIP_TRY(d_blocks.alloc((size_t)n_blocks * sizeof(vmgpu_block_desc)), "alloc descs");
+  VM_HIP_TRY(d_scratch.alloc((size_t)DGRID * DMAX_ROWS * 8), "alloc scratch");
+  VM_HIP_TRY(d_raw_ts.alloc((size_t)total_rows * 8), "alloc raw ts");
+  VM_HIP_TRY(d_raw_vals.alloc((size_t)total_rows * 8), "alloc raw vals");
+  VM_HIP_TRY(d_err.alloc(4), "alloc err");
+  VM_HIP_TRY(hipMemcpyAsync(d_payload.p, payload, payload_len ? payload_len : 1,
+                            hipMemcpyHostToDevice, st), "ul payload");
+  VM_HIP_TRY(hipMemcpyAsync(d_blocks.p, blocks, (size_t)n_blocks * sizeof(vmgpu_block_desc),
+                            hipMemcpyHostToDevice, st), "ul descs");
+  VM_HIP_TRY(hipMemsetAsync(d_err.p, 0, 4, st), "zero err");
+  uint32_t grid = std::min<uint32_t>(n_blocks, DGRID);
   hipLaunchKernelGGL(decode_blocks_kernel, dim3(grid), dim3(DBLOCK), 0, st,
-                     d_payload, d_blocks, n_blocks, d_scratch,
-                     d_raw_ts, d_raw_vals, d_err);
+                     d_payload.p, d_blocks.p, n_blocks, d_scratch.p,
+                     d_raw_ts.p, d_raw_vals.p, d_err.p);
 
-  FDM_TRY(vm_dev_malloc(&d_boff, (size_t)(n_blocks + 1) * 8), "alloc boff");
-  FDM_TRY(vm_dev_malloc(&d_sbs, (size_t)(n_series + 1) * 4), "alloc sbs");
-  FDM_TRY(vm_dev_malloc(&d_capoff, (size_t)(n_series + 1) * 8), "alloc capoff");
-  FDM_TRY(vm_dev_malloc(&d_mts, (cap_off[n_series] ? cap_off[n_series] : 1) * 8), "alloc merged ts");
-  FDM_TRY(vm_dev_malloc(&d_mvals, (cap_off[n_series] ? cap_off[n_series] : 1) * 8), "alloc merged vals");
-  FDM_TRY(vm_dev_malloc(&d_cnt, (size_t)n_series * 8), "alloc counts");
-  FDM_TRY(hipMemcpyAsync(d_boff, boff.data(), (size_t)(n_blocks + 1) * 8,
-                         hipMemcpyHostToDevice, st), "ul boff");
-  FDM_TRY(hipMemcpyAsync(d_sbs, series_block_start, (size_t)(n_series + 1) * 4,
-                         hipMemcpyHostToDevice, st), "ul sbs");
-  FDM_TRY(hipMemcpyAsync(d_capoff, cap_off.data(), (size_t)(n_series + 1) * 8,
-                         hipMemcpyHostToDevice, st), "ul capoff");
-  mgrid = std::min<uint32_t>((n_series + 3) / 4, 2048);
+  VM_HIP_TRY(d_boff.alloc((size_t)(n_blocks + 1) * 8), "alloc boff");
+  VM_HIP_TRY(d_sbs.alloc((size_t)(n_series + 1) * 4), "alloc sbs");
+  VM_HIP_TRY(d_capoff.alloc((size_t)(n_series + 1) * 8), "alloc capoff");
+  VM_HIP_TRY(d_mts.alloc((cap_off[n_series] ? cap_off[n_series] : 1) * 8), "alloc merged ts");
+  VM_HIP_TRY(d_mvals.alloc((cap_off[n_series] ? cap_off[n_series] : 1) * 8), "alloc merged vals");
+  VM_HIP_TRY(d_cnt.alloc((size_t)n_series * 8), "alloc counts");
+  VM_HIP_TRY(hipMemcpyAsync(d_boff.p, boff.data(), (size_t)(n_blocks + 1) * 8,
+                            hipMemcpyHostToDevice, st), "ul boff");
+  VM_HIP_TRY(hipMemcpyAsync(d_sbs.p, series_block_start, (size_t)(n_series + 1) * 4,
+                            hipMemcpyHostToDevice, st), "ul sbs");
+  VM_HIP_TRY(hipMemcpyAsync(d_capoff.p, cap_off.data(), (size_t)(n_series + 1) * 8,
+                            hipMemcpyHostToDevice, st), "ul capoff");
+  uint32_t mgrid = std::min<uint32_t>((n_series + 3) / 4, 2048);
   hipLaunchKernelGGL(merge_blocks_kernel, dim3(mgrid), dim3(DBLOCK), 0, st,
-                     d_raw_ts, d_raw_vals, d_boff, d_sbs, d_capoff, n_series,
-                     dedup_interval, d_mts, d_mvals, d_cnt, d_err);
-  FDM_TRY(hipMemcpyAsync(counts.data(), d_cnt, (size_t)n_series * 8,
-                         hipMemcpyDeviceToHost, st), "dl counts");
-  FDM_TRY(hipMemcpyAsync(&err_h, d_err, 4, hipMemcpyDeviceToHost, st), "dl err");
-  FDM_TRY(hipStreamSynchronize(st), "sync fused");
-  kerr = hipGetLastError();
-  if (kerr != hipSuccess) { rc = dhip_err(errbuf, errbuf_len, "fused kernels", kerr); goto cleanup; }
+                     d_raw_ts.p, d_raw_vals.p, d_boff.p, d_sbs.p, d_capoff.p,
+                     n_series, dedup_interval, d_mts.p, d_mvals.p, d_cnt.p,
+                     d_err.p);
+  VM_HIP_TRY(hipMemcpyAsync(counts.data(), d_cnt.p, (size_t)n_series * 8,
+                            hipMemcpyDeviceToHost, st), "dl counts");
+  VM_HIP_TRY(hipMemcpyAsync(&err_h, d_err.p, 4, hipMemcpyDeviceToHost, st), "dl err");
+  VM_HIP_TRY(hipStreamSynchronize(st), "sync fused");
+  hipError_t kerr = hipGetLastError();
+  if (kerr != hipSuccess) return vm_hip_err(errbuf, errbuf_len, "fused kernels", kerr);
   if (err_h != 0) {
     char msg[64];
     snprintf(msg, sizeof(msg), "vmgpu: fused decode/merge error %d", err_h);
-    rc = dset_err(errbuf, errbuf_len, msg);
-    goto cleanup;
+    return vm_set_err(errbuf, errbuf_len, msg);
   }
 
   h_final_offsets[0] = 0;
   for (uint32_t s = 0; s < n_series; s++)
     h_final_offsets[s + 1] = h_final_offsets[s] + counts[s];
-  FDM_TRY(vm_dev_malloc(&d_finaloff, (size_t)(n_series + 1) * 8), "alloc finaloff");
-  FDM_TRY(hipMemcpyAsync(d_finaloff, h_final_offsets, (size_t)(n_series + 1) * 8,
-                         hipMemcpyHostToDevice, st), "ul finaloff");
+  VM_HIP_TRY(d_finaloff.alloc((size_t)(n_series + 1) * 8), "alloc finaloff");
+  VM_HIP_TRY(hipMemcpyAsync(d_finaloff.p, h_final_offsets, (size_t)(n_series + 1) * 8,
+                            hipMemcpyHostToDevice, st), "ul finaloff");
   /* +16 B slack for the pipe kernel's clamped tail pair load */
-  FDM_TRY(vm_dev_malloc(&d_fts, (h_final_offsets[n_series] ? h_final_offsets[n_series] : 1) * 8 + 16), "alloc final ts");
-  FDM_TRY(vm_dev_malloc(&d_fvals, (h_final_offsets[n_series] ? h_final_offsets[n_series] : 1) * 8 + 16), "alloc final vals");
+  VM_HIP_TRY(d_fts.alloc((h_final_offsets[n_series] ? h_final_offsets[n_series] : 1) * 8 + 16), "alloc final ts");
+  VM_HIP_TRY(d_fvals.alloc((h_final_offsets[n_series] ? h_final_offsets[n_series] : 1) * 8 + 16), "alloc final vals");
   hipLaunchKernelGGL(compact_series_kernel, dim3(mgrid), dim3(DBLOCK), 0, st,
-                     d_mts, d_mvals, d_capoff, d_finaloff, n_series,
-                     d_fts, d_fvals);
-  FDM_TRY(hipStreamSynchronize(st), "sync compact");
+                     d_mts.p, d_mvals.p, d_capoff.p, d_finaloff.p, n_series,
+                     d_fts.p, d_fvals.p);
+  VM_HIP_TRY(hipStreamSynchronize(st), "sync compact");
   kerr = hipGetLastError();
-  if (kerr != hipSuccess) { rc = dhip_err(errbuf, errbuf_len, "compact kernel", kerr); goto cleanup; }
+  if (kerr != hipSuccess) return vm_hip_err(errbuf, errbuf_len, "compact kernel", kerr);
 
-  *out_d_ts = d_fts;
-  *out_d_vals = d_fvals;
-  d_fts = nullptr;
-  d_fvals = nullptr;
-
-cleanup:
-  (void)vm_dev_free(d_payload); (void)vm_dev_free(d_blocks); (void)vm_dev_free(d_scratch);
-  (void)vm_dev_free(d_raw_ts); (void)vm_dev_free(d_raw_vals); (void)vm_dev_free(d_boff);
-  (void)vm_dev_free(d_sbs); (void)vm_dev_free(d_capoff); (void)vm_dev_free(d_mts);
-  (void)vm_dev_free(d_mvals); (void)vm_dev_free(d_cnt); (void)vm_dev_free(d_finaloff);
-  (void)vm_dev_free(d_err); (void)vm_dev_free(d_fts); (void)vm_dev_free(d_fvals);
-#undef FDM_TRY
-  return rc;
+  *out_d_ts = d_fts.release();
+  *out_d_vals = d_fvals.release();
+  return 0;
 }

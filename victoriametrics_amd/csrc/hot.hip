@@ -296,14 +296,14 @@ int vmgpu_vmrange_thresholds_set(const double* thresholds, uint32_t n,
                                  char* errbuf, size_t errbuf_len) {
   std::lock_guard<std::mutex> lock(vm_ctx_mutex());
   if (!vm_ctx_inited())
-    return hot_set_err(errbuf, errbuf_len, "vmgpu: not initialized");
+    return vm_set_err(errbuf, errbuf_len, "vmgpu: not initialized");
   if (!thresholds || n != VMRANGE_N_THRESHOLDS)
-    return hot_set_err(errbuf, errbuf_len,
+    return vm_set_err(errbuf, errbuf_len,
                        "vmgpu: vmrange table must have 487 thresholds");
   for (uint32_t i = 0; i < n; i++) {
     bool ok = thresholds[i] > 0 && (i == 0 || thresholds[i] > thresholds[i - 1]);
     if (!ok)
-      return hot_set_err(errbuf, errbuf_len,
+      return vm_set_err(errbuf, errbuf_len,
                          "vmgpu: vmrange thresholds must be positive and "
                          "strictly increasing");
   }
@@ -312,10 +312,10 @@ int vmgpu_vmrange_thresholds_set(const double* thresholds, uint32_t n,
   for (uint32_t i = n; i < VMRANGE_TABLE_PAD; i++) padded[i] = __builtin_nan("");
   hipStream_t st = vm_ctx_stream();
   if (!g_d_thr)
-    HOT_TRY(vm_dev_malloc(&g_d_thr, sizeof(padded)), "alloc vmrange table");
-  HOT_TRY(hipMemcpyAsync(g_d_thr, padded, sizeof(padded), hipMemcpyHostToDevice, st),
+    VM_HIP_TRY(vm_dev_malloc(&g_d_thr, sizeof(padded)), "alloc vmrange table");
+  VM_HIP_TRY(hipMemcpyAsync(g_d_thr, padded, sizeof(padded), hipMemcpyHostToDevice, st),
           "upload vmrange table");
-  HOT_TRY(hipStreamSynchronize(st), "sync vmrange table");
+  VM_HIP_TRY(hipStreamSynchronize(st), "sync vmrange table");
   return 0;
 }
 
@@ -326,21 +326,21 @@ int vmgpu_histogram_over_time_exec(uint64_t handle, int64_t start, int64_t end,
                                    char* errbuf, size_t errbuf_len) {
   std::lock_guard<std::mutex> lock(vm_ctx_mutex());
   if (!vm_ctx_inited())
-    return hot_set_err(errbuf, errbuf_len, "vmgpu: not initialized");
+    return vm_set_err(errbuf, errbuf_len, "vmgpu: not initialized");
   vm_batch_cols b;
   if (vm_batch_cols_get(handle, &b) != 0)
-    return hot_set_err(errbuf, errbuf_len, "vmgpu: bad handle");
+    return vm_set_err(errbuf, errbuf_len, "vmgpu: bad handle");
   if (window <= 0)
-    return hot_set_err(errbuf, errbuf_len,
+    return vm_set_err(errbuf, errbuf_len,
                        "vmgpu: histogram_over_time needs an explicit window "
                        "(m[d] range selector)");
   if (step <= 0 || end < start)
-    return hot_set_err(errbuf, errbuf_len, "vmgpu: bad grid");
+    return vm_set_err(errbuf, errbuf_len, "vmgpu: bad grid");
   int64_t n_grid64 = 1 + (end - start) / step;
   if (n_grid64 > (int64_t)1 << 30)
-    return hot_set_err(errbuf, errbuf_len, "vmgpu: grid too large");
+    return vm_set_err(errbuf, errbuf_len, "vmgpu: grid too large");
   if (!g_d_thr)
-    return hot_set_err(errbuf, errbuf_len,
+    return vm_set_err(errbuf, errbuf_len,
                        "vmgpu: vmrange threshold table not uploaded "
                        "(vmgpu_vmrange_thresholds_set)");
   HotParams p;
@@ -361,23 +361,23 @@ int vmgpu_histogram_over_time_exec(uint64_t handle, int64_t start, int64_t end,
     /* scratch is sized by the batch, so each piece is allocated once */
     size_t cap = 0;
     if (!h.d_codes)
-      HOT_TRY(hot_reserve(&h.d_codes, &cap, (size_t)b.n_samples * 2 + 16), "alloc codes");
+      VM_HIP_TRY(hot_reserve(&h.d_codes, &cap, (size_t)b.n_samples * 2 + 16), "alloc codes");
     if (!h.d_masks)
-      HOT_TRY(hot_reserve(&h.d_masks, &cap, (size_t)ns * VMRANGE_MASK_WORDS * 4),
+      VM_HIP_TRY(hot_reserve(&h.d_masks, &cap, (size_t)ns * VMRANGE_MASK_WORDS * 4),
               "alloc masks");
     if (!h.d_row_counts)
-      HOT_TRY(hot_reserve(&h.d_row_counts, &cap, (size_t)ns * 4), "alloc row counts");
+      VM_HIP_TRY(hot_reserve(&h.d_row_counts, &cap, (size_t)ns * 4), "alloc row counts");
     if (!h.d_row_start)
-      HOT_TRY(hot_reserve(&h.d_row_start, &cap, ((size_t)ns + 1) * 8), "alloc row start");
+      VM_HIP_TRY(hot_reserve(&h.d_row_start, &cap, ((size_t)ns + 1) * 8), "alloc row start");
     if (!h.d_scanned)
-      HOT_TRY(hot_reserve(&h.d_scanned, &cap, 8), "alloc scanned");
+      VM_HIP_TRY(hot_reserve(&h.d_scanned, &cap, 8), "alloc scanned");
   }
-  HOT_TRY(hipMemsetAsync(h.d_scanned, 0, 8, st), "zero scanned");
+  VM_HIP_TRY(hipMemsetAsync(h.d_scanned, 0, 8, st), "zero scanned");
 
   const uint32_t blocks = std::min<uint32_t>(
       (ns + HOT_WAVES_PER_BLOCK - 1) / HOT_WAVES_PER_BLOCK, HOT_MAX_BLOCKS);
 
-  HOT_TRY(hipEventRecord(ev_start, st), "event start");
+  VM_HIP_TRY(hipEventRecord(ev_start, st), "event start");
   hipLaunchKernelGGL(hot_mark_kernel, dim3(blocks), dim3(HOT_BLOCK_THREADS), 0, st,
                      p, b.d_ts, b.d_vals, b.d_offsets, g_d_thr, ns,
                      h.d_codes, h.d_masks, h.d_row_counts, h.d_scanned);
@@ -385,37 +385,37 @@ int vmgpu_histogram_over_time_exec(uint64_t handle, int64_t start, int64_t end,
   /* the output size is data-dependent: the host learns n_rows here */
   uint64_t n_rows = 0;
   unsigned long long scanned_h = 0;
-  HOT_TRY(hipMemcpyAsync(&n_rows, h.d_row_start + ns, 8, hipMemcpyDeviceToHost, st),
+  VM_HIP_TRY(hipMemcpyAsync(&n_rows, h.d_row_start + ns, 8, hipMemcpyDeviceToHost, st),
           "download n_rows");
-  HOT_TRY(hipMemcpyAsync(&scanned_h, h.d_scanned, 8, hipMemcpyDeviceToHost, st),
+  VM_HIP_TRY(hipMemcpyAsync(&scanned_h, h.d_scanned, 8, hipMemcpyDeviceToHost, st),
           "download scanned");
-  HOT_TRY(hipStreamSynchronize(st), "sync mark");
+  VM_HIP_TRY(hipStreamSynchronize(st), "sync mark");
   {
     hipError_t kerr = hipGetLastError();
-    if (kerr != hipSuccess) return hot_hip_err(errbuf, errbuf_len, "mark kernel", kerr);
+    if (kerr != hipSuccess) return vm_hip_err(errbuf, errbuf_len, "mark kernel", kerr);
   }
   if (n_rows > (uint64_t)ns * VMRANGE_N_CODES)
-    return hot_set_err(errbuf, errbuf_len, "vmgpu: inconsistent row count");
+    return vm_set_err(errbuf, errbuf_len, "vmgpu: inconsistent row count");
 
   h.n_rows = n_rows;
   h.n_grid = p.n_grid;
   if (n_rows) {
-    HOT_TRY(hot_reserve(&h.d_out, &h.out_cap, (size_t)n_rows * p.n_grid * 8),
+    VM_HIP_TRY(hot_reserve(&h.d_out, &h.out_cap, (size_t)n_rows * p.n_grid * 8),
             "alloc histogram rows");
-    HOT_TRY(hot_reserve(&h.d_row_series, &h.row_series_cap, (size_t)n_rows * 4),
+    VM_HIP_TRY(hot_reserve(&h.d_row_series, &h.row_series_cap, (size_t)n_rows * 4),
             "alloc row series");
-    HOT_TRY(hot_reserve(&h.d_row_code, &h.row_code_cap, (size_t)n_rows * 2),
+    VM_HIP_TRY(hot_reserve(&h.d_row_code, &h.row_code_cap, (size_t)n_rows * 2),
             "alloc row codes");
     hipLaunchKernelGGL(hot_count_kernel, dim3(blocks), dim3(HOT_BLOCK_THREADS), 0, st,
                        p, b.d_ts, h.d_codes, b.d_offsets, h.d_masks,
                        h.d_row_start, ns, h.d_out, h.d_row_series,
                        h.d_row_code);
   }
-  HOT_TRY(hipEventRecord(ev_stop, st), "event stop");
-  HOT_TRY(hipStreamSynchronize(st), "sync count");
-  HOT_TRY(hipGetLastError(), "count kernel");
+  VM_HIP_TRY(hipEventRecord(ev_stop, st), "event stop");
+  VM_HIP_TRY(hipStreamSynchronize(st), "sync count");
+  VM_HIP_TRY(hipGetLastError(), "count kernel");
   float ms = 0;
-  HOT_TRY(hipEventElapsedTime(&ms, ev_start, ev_stop), "event elapsed");
+  VM_HIP_TRY(hipEventElapsedTime(&ms, ev_start, ev_stop), "event elapsed");
   vm_ctx_set_last_kernel_ms((double)ms);
   h.valid = true;
   if (out_n_rows) *out_n_rows = n_rows;
@@ -428,31 +428,31 @@ int vmgpu_histogram_over_time_fetch(uint64_t handle, uint32_t* row_series,
                                     char* errbuf, size_t errbuf_len) {
   std::lock_guard<std::mutex> lock(vm_ctx_mutex());
   if (!vm_ctx_inited())
-    return hot_set_err(errbuf, errbuf_len, "vmgpu: not initialized");
+    return vm_set_err(errbuf, errbuf_len, "vmgpu: not initialized");
   vm_batch_cols b;
   if (vm_batch_cols_get(handle, &b) != 0)
-    return hot_set_err(errbuf, errbuf_len, "vmgpu: bad handle");
+    return vm_set_err(errbuf, errbuf_len, "vmgpu: bad handle");
   const vm_hot_state& h = *b.hot;
   if (!h.valid)
-    return hot_set_err(errbuf, errbuf_len,
+    return vm_set_err(errbuf, errbuf_len,
                        "vmgpu: no histogram_over_time result on this batch");
   if (h.n_rows == 0) return 0;
   hipStream_t st = vm_ctx_stream();
   if (row_series)
-    HOT_TRY(hipMemcpyAsync(row_series, h.d_row_series, h.n_rows * 4,
+    VM_HIP_TRY(hipMemcpyAsync(row_series, h.d_row_series, h.n_rows * 4,
                            hipMemcpyDeviceToHost, st), "download row series");
   if (row_bucket)
-    HOT_TRY(hipMemcpyAsync(row_bucket, h.d_row_code, h.n_rows * 2,
+    VM_HIP_TRY(hipMemcpyAsync(row_bucket, h.d_row_code, h.n_rows * 2,
                            hipMemcpyDeviceToHost, st), "download row buckets");
   if (out)
-    HOT_TRY(hipMemcpyAsync(out, h.d_out, (size_t)h.n_rows * h.n_grid * 8,
+    VM_HIP_TRY(hipMemcpyAsync(out, h.d_out, (size_t)h.n_rows * h.n_grid * 8,
                            hipMemcpyDeviceToHost, st), "download histogram rows");
-  HOT_TRY(hipStreamSynchronize(st), "sync fetch");
+  VM_HIP_TRY(hipStreamSynchronize(st), "sync fetch");
   if (row_series && b.perm)
     for (uint64_t i = 0; i < h.n_rows; i++) {
       uint32_t phys = row_series[i];
       if (phys >= b.n_series)
-        return hot_set_err(errbuf, errbuf_len, "vmgpu: corrupt row series");
+        return vm_set_err(errbuf, errbuf_len, "vmgpu: corrupt row series");
       row_series[i] = b.perm[phys];
     }
   return 0;

@@ -6,7 +6,8 @@
 #define VMGPU_HOT_COMMON_H
 #include <hip/hip_runtime.h>
 #include <stdint.h>
-#include <cstdio>
+
+#include "host_common.h"
 
 #define HOT_WAVE 64
 #define HOT_BLOCK_THREADS 256
@@ -68,16 +69,6 @@ static HOT_DEV bool hot_grid_range(const HotParams& p, int64_t ts,
 void hot_scan_launch(const uint32_t* row_counts, uint32_t n,
                      uint64_t* row_start, hipStream_t st);
 
-inline int hot_set_err(char* errbuf, size_t len, const char* msg) {
-  if (errbuf && len) snprintf(errbuf, len, "%s", msg);
-  return 1;
-}
-
-inline int hot_hip_err(char* errbuf, size_t len, const char* what, hipError_t e) {
-  if (errbuf && len) snprintf(errbuf, len, "%s: %s", what, hipGetErrorString(e));
-  return 2;
-}
-
 /* Grow-only reservation with plain hipMalloc.  Deliberately NOT the
  * stream-ordered pool of devalloc.h: the result size changes from call to
  * call, and a free-then-larger-malloc cycle through the pool right before
@@ -94,11 +85,5 @@ inline hipError_t hot_reserve(T** p, size_t* cap, size_t bytes) {
   if (e == hipSuccess) *cap = bytes;
   return e;
 }
-
-#define HOT_TRY(expr, what)                                                \
-  do {                                                                     \
-    hipError_t _e = (expr);                                                \
-    if (_e != hipSuccess) return hot_hip_err(errbuf, errbuf_len, what, _e); \
-  } while (0)
 
 #endif

@@ -31,33 +31,8 @@
 #include <algorithm>
 #include <cstdio>
 
+#include "host_common.h"
 #include "../../include/vmgpu.h"
-
-namespace {
-
-int tset_err(char* errbuf, size_t len, const char* msg) {
-  if (errbuf && len) snprintf(errbuf, len, "%s", msg);
-  return 1;
-}
-
-int thip_err(char* errbuf, size_t len, const char* what, hipError_t e) {
-  if (errbuf && len) snprintf(errbuf, len, "%s: %s", what, hipGetErrorString(e));
-  return 2;
-}
-
-#define THIP_TRY(expr, what)                                               \
-  do {                                                                     \
-    hipError_t _e = (expr);                                                \
-    if (_e != hipSuccess) return thip_err(errbuf, errbuf_len, what, _e);   \
-  } while (0)
-
-struct TDevBuf {
-  void* p = nullptr;
-  ~TDevBuf() { if (p) (void)hipFree(p); }
-  hipError_t alloc(size_t n) { return hipMalloc(&p, n ? n : 1); }
-};
-
-}  // namespace
 
 static __device__ __forceinline__ double t_nan() {
   return __longlong_as_double(0x7ff8000000000000LL);
@@ -550,28 +525,28 @@ int vmgpu_transform(int32_t func, double* values, uint32_t n_series,
                     const double* arg2, double scalar_arg,
                     uint8_t* keep_flags, char* errbuf, size_t errbuf_len) {
   if (!values || n_series == 0 || n_grid == 0)
-    return tset_err(errbuf, errbuf_len, "vmgpu: bad transform args");
+    return vm_set_err(errbuf, errbuf_len, "vmgpu: bad transform args");
   hipStream_t st = 0;
   size_t vbytes = (size_t)n_series * n_grid * 8;
-  TDevBuf dv, dts, da1, da2, dscr, dkeep;
-  THIP_TRY(dv.alloc(vbytes), "alloc tf values");
-  THIP_TRY(hipMemcpyAsync(dv.p, values, vbytes, hipMemcpyHostToDevice, st), "ul tf");
+  VmDevBuf dv, dts, da1, da2, dscr, dkeep;
+  VM_HIP_TRY(dv.alloc(vbytes), "alloc tf values");
+  VM_HIP_TRY(hipMemcpyAsync(dv.p, values, vbytes, hipMemcpyHostToDevice, st), "ul tf");
   const int64_t* d_ts = nullptr;
   const double* d_a1 = nullptr;
   const double* d_a2 = nullptr;
   if (ts) {
-    THIP_TRY(dts.alloc((size_t)n_grid * 8), "alloc tf ts");
-    THIP_TRY(hipMemcpyAsync(dts.p, ts, (size_t)n_grid * 8, hipMemcpyHostToDevice, st), "ul tf ts");
+    VM_HIP_TRY(dts.alloc((size_t)n_grid * 8), "alloc tf ts");
+    VM_HIP_TRY(hipMemcpyAsync(dts.p, ts, (size_t)n_grid * 8, hipMemcpyHostToDevice, st), "ul tf ts");
     d_ts = (const int64_t*)dts.p;
   }
   if (arg1) {
-    THIP_TRY(da1.alloc((size_t)n_grid * 8), "alloc tf a1");
-    THIP_TRY(hipMemcpyAsync(da1.p, arg1, (size_t)n_grid * 8, hipMemcpyHostToDevice, st), "ul tf a1");
+    VM_HIP_TRY(da1.alloc((size_t)n_grid * 8), "alloc tf a1");
+    VM_HIP_TRY(hipMemcpyAsync(da1.p, arg1, (size_t)n_grid * 8, hipMemcpyHostToDevice, st), "ul tf a1");
     d_a1 = (const double*)da1.p;
   }
   if (arg2) {
-    THIP_TRY(da2.alloc((size_t)n_grid * 8), "alloc tf a2");
-    THIP_TRY(hipMemcpyAsync(da2.p, arg2, (size_t)n_grid * 8, hipMemcpyHostToDevice, st), "ul tf a2");
+    VM_HIP_TRY(da2.alloc((size_t)n_grid * 8), "alloc tf a2");
+    VM_HIP_TRY(hipMemcpyAsync(da2.p, arg2, (size_t)n_grid * 8, hipMemcpyHostToDevice, st), "ul tf a2");
     d_a2 = (const double*)da2.p;
   }
   bool elementwise = func < VMGPU_TF_SERIES_BASE;
@@ -588,12 +563,12 @@ int vmgpu_transform(int32_t func, double* values, uint32_t n_series,
                           func == VMGPU_TF_RANGE_QUANTILE);
     double* d_scr = nullptr;
     if (needs_scratch) {
-      THIP_TRY(dscr.alloc(vbytes), "alloc tf scratch");
+      VM_HIP_TRY(dscr.alloc(vbytes), "alloc tf scratch");
       d_scr = (double*)dscr.p;
     }
     uint8_t* d_keep = nullptr;
     if (keep_flags) {
-      THIP_TRY(dkeep.alloc(n_series), "alloc tf keep");
+      VM_HIP_TRY(dkeep.alloc(n_series), "alloc tf keep");
       d_keep = (uint8_t*)dkeep.p;
     }
     uint32_t blocks = std::min<uint32_t>((n_series + 255) / 256, 4096);
@@ -601,13 +576,13 @@ int vmgpu_transform(int32_t func, double* values, uint32_t n_series,
                        func, (double*)dv.p, (uint64_t)n_series, n_grid, d_ts,
                        d_a1, scalar_arg, d_scr, d_keep);
     if (keep_flags)
-      THIP_TRY(hipMemcpyAsync(keep_flags, dkeep.p, n_series,
+      VM_HIP_TRY(hipMemcpyAsync(keep_flags, dkeep.p, n_series,
                               hipMemcpyDeviceToHost, st), "dl tf keep");
   }
-  THIP_TRY(hipMemcpyAsync(values, dv.p, vbytes, hipMemcpyDeviceToHost, st), "dl tf");
-  THIP_TRY(hipStreamSynchronize(st), "sync tf");
+  VM_HIP_TRY(hipMemcpyAsync(values, dv.p, vbytes, hipMemcpyDeviceToHost, st), "dl tf");
+  VM_HIP_TRY(hipStreamSynchronize(st), "sync tf");
   hipError_t kerr = hipGetLastError();
-  if (kerr != hipSuccess) return thip_err(errbuf, errbuf_len, "tf kernel", kerr);
+  if (kerr != hipSuccess) return vm_hip_err(errbuf, errbuf_len, "tf kernel", kerr);
   return 0;
 }
 

@@ -27,6 +27,12 @@
  * the 1M-series rollup never materializes per-series grids in HBM.  The
  * multi-GPU merge all-reduces those matrices BEFORE the
  * finalize step; plan->skip_finalize exposes exactly that cut.
+ *
+ * This file also owns the context (stream, pool, events) and the resident
+ * Batch with its one builder.  What runs over a batch or its output without
+ * sharing these kernels lives in files of its own and reaches the context
+ * through batch_access.h and devalloc.h: hot.hip, cvot.hip, topk.hip (the
+ * topk family) and hstat.hip (the histogram transforms).
  */
 #include <hip/hip_runtime.h>
 #include <algorithm>
@@ -39,7 +45,7 @@
 #include <vector>
 
 #include "batch_access.h"
-#include "devalloc.h"
+#include "host_common.h"
 #include "rollup_device.h"
 #include "vm_div1e3.h"
 #include "../../include/vmgpu.h"
@@ -2350,574 +2356,6 @@ __global__ void aggr_finalize_kernel(double* values, double* counts, uint64_t n,
   }
 }
 
-
-/* ------------------------------------------------------------------ */
-/* topk family (aggr.go:646-741) + histogram_quantile (transform.go)  */
-/* ------------------------------------------------------------------ */
-
-/* Order-preserving u64 key for f64 under lessWithNaNs / greaterWithNaNs
- * (aggr.go:1259-1279): selection always keeps the "k largest keys".  NaN
- * maps to the SMALLEST key in both directions — lessWithNaNs treats NaN as
- * smaller than any number (so topk never keeps it) and greaterWithNaNs
- * treats it as bigger (so it sorts to the FRONT of the bottomk order and
- * is again never kept). */
-static VM_DEV unsigned long long vm_topk_key(double v, int reverse) {
-  if (vm_isnan(v)) return 0ULL;
-  unsigned long long b = (unsigned long long)__double_as_longlong(v);
-  unsigned long long ord = (b >> 63) ? ~b : (b | 0x8000000000000000ULL);
-  /* the NaN sentinels 0 and ~0 are unreachable for non-NaN doubles: their
-   * preimages under the order map are NaN bit patterns */
-  return reverse ? ~ord : ord;
-}
-
-/* inverse of vm_topk_key's order map (non-NaN keys only) */
-static VM_DEV double vm_topk_key_inv(unsigned long long ord) {
-  unsigned long long b = (ord & 0x8000000000000000ULL)
-                             ? (ord ^ 0x8000000000000000ULL)
-                             : ~ord;
-  return __longlong_as_double((long long)b);
-}
-
-/* k-th smallest (0-based) non-NaN key of a row: 8 passes of 256-bin LDS
- * histogram refinement over the order-preserving u64 keys (exact — every
- * byte of the result is pinned by counts).  hist: per-wave uint32[256]. */
-static __device__ unsigned long long topk_row_kth(
-    const double* row, int32_t n_grid, uint32_t k, int lane, uint32_t* hist) {
-  unsigned long long prefix = 0;
-  for (int byte = 7; byte >= 0; byte--) {
-    const int shift = byte * 8;
-    for (int b = lane; b < 256; b += WAVE) hist[b] = 0;
-    wave_ds_sync();
-    const unsigned long long pmask =
-        (byte == 7) ? 0ULL : (~0ULL << (shift + 8));
-    for (int g = lane; g < n_grid; g += WAVE) {
-      double v = row[g];
-      if (vm_isnan(v)) continue;
-      unsigned long long key = vm_topk_key(v, 0);
-      if ((key & pmask) != prefix) continue;
-      atomicAdd(&hist[(key >> shift) & 0xff], 1u);
-    }
-    wave_ds_sync();
-    /* each lane owns 4 consecutive bins; exclusive wave prefix of totals */
-    uint32_t b0 = hist[lane * 4], b1 = hist[lane * 4 + 1];
-    uint32_t b2 = hist[lane * 4 + 2], b3 = hist[lane * 4 + 3];
-    uint32_t lt = b0 + b1 + b2 + b3;
-    uint32_t ex = lt;
-    for (int d = 1; d < WAVE; d <<= 1) {
-      uint32_t xo = __shfl_up(ex, d);
-      if (lane >= d) ex += xo;
-    }
-    ex -= lt;
-    uint32_t c0 = ex, c1 = c0 + b0, c2 = c1 + b1, c3 = c2 + b2;
-    int pick = -1;
-    if (k >= c0 && k < c0 + b0) pick = 0;
-    else if (k >= c1 && k < c1 + b1) pick = 1;
-    else if (k >= c2 && k < c2 + b2) pick = 2;
-    else if (k >= c3 && k < c3 + b3) pick = 3;
-    uint64_t mb = __ballot(pick >= 0);
-    int srcl = __ffsll((unsigned long long)mb) - 1;
-    int pickv = __shfl(pick, srcl);
-    uint32_t below = __shfl(pickv == 0 ? c0 : pickv == 1 ? c1
-                            : pickv == 2 ? c2 : c3, srcl);
-    int bin = srcl * 4 + pickv;
-    k -= below;
-    prefix |= ((unsigned long long)(unsigned)bin) << shift;
-    wave_ds_sync();
-  }
-  return prefix;
-}
-
-/* per-series range summaries (aggr.go:804-858), one wave per series row */
-__global__ __launch_bounds__(BLOCK_THREADS) void topk_summary_kernel(
-    const double* values, uint32_t n_series, int32_t n_grid, int32_t op,
-    int32_t reverse, unsigned long long* keys) {
-  __shared__ uint32_t sh_hist[WAVES_PER_BLOCK][256];
-  const int wave_in_block = threadIdx.x / WAVE;
-  const int lane = threadIdx.x % WAVE;
-  uint32_t wid = blockIdx.x * WAVES_PER_BLOCK + wave_in_block;
-  uint32_t stride = gridDim.x * WAVES_PER_BLOCK;
-  for (uint32_t s = wid; s < n_series; s += stride) {
-    const double* row = values + (size_t)s * n_grid;
-    double acc = vm_dnan();
-    if (op == 0 || op == 1 || op == 2) { /* avg / min / max */
-      double sum = 0, cnt = 0;
-      double mn = vm_dnan(), mx = vm_dnan();
-      for (int g = lane; g < n_grid; g += WAVE) {
-        double v = row[g];
-        if (vm_isnan(v)) continue;
-        cnt += 1;
-        sum += v;
-        if (vm_isnan(mn) || v < mn) mn = v;
-        if (vm_isnan(mx) || v > mx) mx = v;
-      }
-      for (int d = 32; d > 0; d >>= 1) {
-        double so = __shfl_down(sum, d);
-        double co = __shfl_down(cnt, d);
-        double mno = __shfl_down(mn, d);
-        double mxo = __shfl_down(mx, d);
-        sum += so;
-        cnt += co;
-        if (vm_isnan(mn) || (!vm_isnan(mno) && mno < mn)) mn = mno;
-        if (vm_isnan(mx) || (!vm_isnan(mxo) && mxo > mx)) mx = mxo;
-      }
-      if (op == 0) acc = (cnt == 0) ? vm_dnan() : sum / cnt;
-      else if (op == 1) acc = mn;
-      else acc = mx;
-    } else if (op == 3) { /* median = quantile(0.5) (aggr.go:848,922) */
-      uint32_t m = 0;
-      for (int g = lane; g < n_grid; g += WAVE)
-        if (!vm_isnan(row[g])) m++;
-      for (int d = 32; d > 0; d >>= 1) m += __shfl_down(m, d);
-      m = __shfl(m, 0);
-      if (m > 0) {
-        uint32_t li = (m - 1) / 2; /* floor(0.5*(m-1)) */
-        unsigned long long kv =
-            topk_row_kth(row, n_grid, li, lane, sh_hist[wave_in_block]);
-        double vlo = vm_topk_key_inv(kv);
-        if (m & 1) {
-          acc = vlo; /* odd count: weight 0 */
-        } else {
-          /* upper = positional li+1 in the sorted row: equals vlo inside
-           * an equal run, else the smallest key > kv */
-          uint32_t cle = 0; /* #keys <= kv */
-          unsigned long long nxt = ~0ULL;
-          for (int g = lane; g < n_grid; g += WAVE) {
-            double v = row[g];
-            if (vm_isnan(v)) continue;
-            unsigned long long key = vm_topk_key(v, 0);
-            if (key <= kv) cle++;
-            else if (key < nxt) nxt = key;
-          }
-          for (int d = 32; d > 0; d >>= 1) {
-            cle += __shfl_down(cle, d);
-            unsigned long long no = __shfl_down(nxt, d);
-            if (no < nxt) nxt = no;
-          }
-          cle = __shfl(cle, 0);
-          nxt = __shfl(nxt, 0);
-          double vhi = (li + 1 < cle) ? vlo : vm_topk_key_inv(nxt);
-          /* quantileSorted: v[lower]*(1-weight) + v[upper]*weight, w=0.5 */
-          acc = vlo * 0.5 + vhi * 0.5;
-        }
-      }
-    } else if (op == 4) { /* last non-NaN */
-      int base = ((n_grid + WAVE - 1) / WAVE - 1) * WAVE;
-      for (; base >= 0; base -= WAVE) {
-        int g = base + lane;
-        double v = (g < n_grid) ? row[g] : vm_dnan();
-        uint64_t m = __ballot(!vm_isnan(v));
-        if (m) {
-          int hi = 63 - __clzll((unsigned long long)m);
-          acc = __shfl(v, hi);
-          break;
-        }
-      }
-    }
-    if (lane == 0) keys[s] = vm_topk_key(acc, reverse);
-  }
-}
-
-__global__ void topk_hist_kernel(const unsigned long long* keys, uint32_t n,
-                                 unsigned long long prefix, int shift,
-                                 uint32_t* hist) {
-  /* 16-bit histogram of keys whose bits above shift+16 equal prefix */
-  uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-  uint32_t stride = gridDim.x * blockDim.x;
-  for (; i < n; i += stride) {
-    unsigned long long k = keys[i];
-    if (shift < 48 && (k >> (shift + 16)) != prefix) continue;
-    atomicAdd(&hist[(k >> shift) & 0xffff], 1u);
-  }
-}
-
-__global__ void topk_collect_kernel(const unsigned long long* keys, uint32_t n,
-                                    unsigned long long kstar, uint32_t ties_quota,
-                                    uint32_t* counters, uint32_t* sel,
-                                    uint32_t sel_cap) {
-  uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-  uint32_t stride = gridDim.x * blockDim.x;
-  for (; i < n; i += stride) {
-    unsigned long long k = keys[i];
-    if (k > kstar) {
-      uint32_t slot = atomicAdd(&counters[0], 1u);
-      if (slot < sel_cap) sel[slot] = i;
-    } else if (k == kstar) {
-      uint32_t t = atomicAdd(&counters[1], 1u);
-      if (t < ties_quota) {
-        uint32_t slot = atomicAdd(&counters[0], 1u);
-        if (slot < sel_cap) sel[slot] = i;
-      }
-    }
-  }
-}
-
-__global__ void topk_remaining_kernel(const double* values, uint32_t n_series,
-                                      int32_t n_grid, const uint8_t* selected,
-                                      double* rem_sum, double* rem_cnt) {
-  size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  size_t total = (size_t)n_series * n_grid;
-  size_t stride = (size_t)gridDim.x * blockDim.x;
-  for (; i < total; i += stride) {
-    uint32_t s = (uint32_t)(i / n_grid);
-    int32_t g = (int32_t)(i % n_grid);
-    if (selected[s]) continue;
-    double v = values[i];
-    if (vm_isnan(v)) continue;
-    atomicAdd(&rem_sum[g], v);
-    atomicAdd(&rem_cnt[g], 1.0);
-  }
-}
-
-/* ---- pointwise topk over [n_series x n_grid] ---- */
-
-__global__ void topk_col_hist_kernel(const double* values, uint32_t n_series,
-                                     int32_t n_grid, int32_t reverse,
-                                     uint32_t* hists) {
-  size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  size_t total = (size_t)n_series * n_grid;
-  size_t stride = (size_t)gridDim.x * blockDim.x;
-  for (; i < total; i += stride) {
-    int32_t g = (int32_t)(i % n_grid);
-    unsigned long long k = vm_topk_key(values[i], reverse);
-    atomicAdd(&hists[(size_t)g * 65536 + (k >> 48)], 1u);
-  }
-}
-
-__global__ void topk_col_threshold_kernel(const uint32_t* hists, int32_t n_grid,
-                                          uint32_t k, uint32_t* bin_of_col,
-                                          uint32_t* above_of_col) {
-  int g = blockIdx.x * blockDim.x + threadIdx.x;
-  if (g >= n_grid) return;
-  const uint32_t* h = hists + (size_t)g * 65536;
-  uint32_t cum = 0;
-  int bin = 0;
-  for (int b = 65535; b >= 0; b--) {
-    uint32_t c = h[b];
-    if (cum + c >= k) {
-      bin = b;
-      break;
-    }
-    cum += c;
-  }
-  bin_of_col[g] = (uint32_t)bin;
-  above_of_col[g] = cum;
-}
-
-__global__ void topk_col_candidates_kernel(const double* values, uint32_t n_series,
-                                           int32_t n_grid, int32_t reverse,
-                                           const uint32_t* bin_of_col,
-                                           unsigned long long* cand,
-                                           uint32_t* cand_n, uint32_t cap,
-                                           uint32_t* overflow) {
-  size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  size_t total = (size_t)n_series * n_grid;
-  size_t stride = (size_t)gridDim.x * blockDim.x;
-  for (; i < total; i += stride) {
-    int32_t g = (int32_t)(i % n_grid);
-    unsigned long long k = vm_topk_key(values[i], reverse);
-    if ((uint32_t)(k >> 48) != bin_of_col[g]) continue;
-    uint32_t slot = atomicAdd(&cand_n[g], 1u);
-    if (slot < cap) cand[(size_t)g * cap + slot] = k;
-    else atomicAdd(overflow, 1u);
-  }
-}
-
-__global__ __launch_bounds__(256) void topk_col_kstar_kernel(
-    const unsigned long long* cand, const uint32_t* cand_n, uint32_t cap,
-    const uint32_t* above_of_col, uint32_t k, int32_t n_grid,
-    unsigned long long* kstar_of_col, uint32_t* ties_of_col) {
-  int g = blockIdx.x;
-  if (g >= n_grid) return;
-  uint32_t n = cand_n[g];
-  if (n > cap) n = cap;
-  uint32_t need = k > above_of_col[g] ? k - above_of_col[g] : 0;
-  const unsigned long long* c = cand + (size_t)g * cap;
-  __shared__ unsigned long long sh_lo, sh_hi, sh_mid;
-  __shared__ uint32_t sh_cnt;
-  if (threadIdx.x == 0) {
-    sh_lo = 0;
-    sh_hi = ~0ULL;
-  }
-  __syncthreads();
-  if (need == 0 || n == 0) {
-    if (threadIdx.x == 0) {
-      kstar_of_col[g] = ~0ULL;
-      ties_of_col[g] = 0;
-    }
-    return;
-  }
-  for (int it = 0; it < 64; it++) {
-    if (threadIdx.x == 0) {
-      sh_mid = sh_lo + ((sh_hi - sh_lo) >> 1);
-      sh_cnt = 0;
-    }
-    __syncthreads();
-    unsigned long long mid = sh_mid;
-    uint32_t local = 0;
-    for (uint32_t t = threadIdx.x; t < n; t += blockDim.x)
-      if (c[t] >= mid) local++;
-    atomicAdd(&sh_cnt, local);
-    __syncthreads();
-    bool done = false;
-    if (threadIdx.x == 0) {
-      if (sh_cnt >= need) sh_lo = sh_mid + 1;
-      else sh_hi = sh_mid;
-    }
-    __syncthreads();
-    if (sh_lo >= sh_hi) { done = true; }
-    if (done) break;
-  }
-  unsigned long long kstar = sh_lo - 1;
-  if (threadIdx.x == 0) sh_cnt = 0;
-  __syncthreads();
-  uint32_t local = 0;
-  for (uint32_t t = threadIdx.x; t < n; t += blockDim.x)
-    if (c[t] > kstar) local++;
-  atomicAdd(&sh_cnt, local);
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    kstar_of_col[g] = kstar;
-    ties_of_col[g] = need - sh_cnt;
-  }
-}
-
-__global__ void topk_col_fill_kernel(double* values, uint32_t n_series,
-                                     int32_t n_grid, int32_t reverse, uint32_t k,
-                                     const uint32_t* bin_of_col,
-                                     const unsigned long long* kstar_of_col,
-                                     uint32_t* ties_taken,
-                                     const uint32_t* ties_of_col) {
-  size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  size_t total = (size_t)n_series * n_grid;
-  size_t stride = (size_t)gridDim.x * blockDim.x;
-  for (; i < total; i += stride) {
-    int32_t g = (int32_t)(i % n_grid);
-    unsigned long long key = vm_topk_key(values[i], reverse);
-    uint32_t bin = bin_of_col[g];
-    uint32_t kb = (uint32_t)(key >> 48);
-    bool keep;
-    if (kb > bin) {
-      keep = true;
-    } else if (kb < bin) {
-      keep = false;
-    } else {
-      unsigned long long kstar = kstar_of_col[g];
-      if (key > kstar) keep = true;
-      else if (key == kstar) {
-        uint32_t t = atomicAdd(&ties_taken[g], 1u);
-        keep = t < ties_of_col[g];
-      } else {
-        keep = false;
-      }
-    }
-    if (!keep) values[i] = vm_dnan();
-  }
-}
-
-/* histogram_quantile (transform.go:1028-1074 + fixBrokenBuckets 1140):
- * one thread per (group, grid point) */
-/* histogram_avg / histogram_stddev / histogram_stdvar
- * (transform.go:transformHistogramAvg/Stddev/Stdvar + avgForLeTimeseries /
- * stdvarForLeTimeseries): (le+lePrev)/2-weighted moments over the bucket
- * column, +/-Inf les skipped, NO fixBrokenBuckets (the reference reads raw
- * cumulative values here). mode: 0 avg, 1 stddev, 2 stdvar. */
-__global__ void hstat_kernel(int32_t mode, const double* bv, const double* les,
-                             const uint64_t* goff, int64_t n_groups,
-                             int32_t n_grid, double* out) {
-  size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  size_t total = (size_t)n_groups * n_grid;
-  size_t stride = (size_t)gridDim.x * blockDim.x;
-  for (; i < total; i += stride) {
-    int64_t grp = (int64_t)(i / n_grid);
-    int32_t g = (int32_t)(i % n_grid);
-    int64_t lo = (int64_t)goff[grp];
-    int64_t n_les = (int64_t)(goff[grp + 1] - lo);
-    double le_prev = 0, v_prev = 0, sum = 0, sum2 = 0, wt = 0;
-    for (int64_t j = 0; j < n_les; j++) {
-      double le = les[lo + j];
-      if (isinf(le)) continue;
-      double v = bv[(size_t)(lo + j) * n_grid + g];
-      double n = (le + le_prev) / 2;
-      double w = v - v_prev;
-      sum += n * w;
-      sum2 += n * n * w;
-      wt += w;
-      le_prev = le;
-      v_prev = v;
-    }
-    double r;
-    if (wt == 0) {
-      r = vm_dnan();
-    } else if (mode == 0) {
-      r = sum / wt;
-    } else {
-      double avg = sum / wt;
-      double sv = sum2 / wt - avg * avg;
-      if (sv < 0) sv = 0;
-      r = (mode == 1) ? sqrt(sv) : sv;
-    }
-    out[i] = r;
-  }
-}
-
-/* histogram_share (transform.go:transformHistogramShare): the quantile
- * walk's dual — share of samples <= leReq[g], with lower/upper bounds.
- * fixBrokenBuckets applied on the fly as in hq_kernel. */
-__global__ void hshare_kernel(const double* le_req, const double* bv,
-                              const double* les, const uint64_t* goff,
-                              int64_t n_groups, int32_t n_grid, double* out,
-                              double* out_lo, double* out_hi) {
-  size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  size_t total = (size_t)n_groups * n_grid;
-  size_t stride = (size_t)gridDim.x * blockDim.x;
-  for (; i < total; i += stride) {
-    int64_t grp = (int64_t)(i / n_grid);
-    int32_t g = (int32_t)(i % n_grid);
-    int64_t lo = (int64_t)goff[grp];
-    int64_t n_les = (int64_t)(goff[grp + 1] - lo);
-    double req = le_req[g];
-    double q = vm_dnan(), lb = vm_dnan(), ub = vm_dnan();
-    if (!vm_isnan(req) && n_les > 0) {
-      if (req < 0) {
-        q = 0; lb = 0; ub = 0;
-      } else if (isinf(req) && req > 0) {
-        q = 1; lb = 1; ub = 1;
-      } else {
-        /* fixBrokenBuckets pass: running-max with NaN->prev */
-        double v_last = 0;
-        {
-          double fix_prev = 0;
-          for (int64_t j = 0; j < n_les; j++) {
-            double v = bv[(size_t)(lo + j) * n_grid + g];
-            if (j == 0) fix_prev = vm_isnan(v) ? 0 : v;
-            else if (!(vm_isnan(v) || fix_prev > v)) fix_prev = v;
-          }
-          v_last = fix_prev;
-        }
-        double vp = 0, lep = 0;
-        double fix_prev = 0;
-        bool done = false;
-        for (int64_t j = 0; j < n_les && !done; j++) {
-          double raw = bv[(size_t)(lo + j) * n_grid + g];
-          double v;
-          if (j == 0) v = vm_isnan(raw) ? 0 : raw;
-          else v = (vm_isnan(raw) || fix_prev > raw) ? fix_prev : raw;
-          fix_prev = v;
-          double le = les[lo + j];
-          if (req >= le) {
-            vp = v;
-            lep = le;
-            continue;
-          }
-          /* lePrev <= req < le */
-          lb = vp / v_last;
-          if (isinf(le) && le > 0) {
-            q = lb;
-            ub = 1;
-          } else if (lep == req) {
-            q = lb;
-            ub = lb;
-          } else {
-            ub = v / v_last;
-            q = lb + (v - vp) / v_last * (req - lep) / (le - lep);
-          }
-          done = true;
-        }
-        if (!done) { q = 1; lb = 1; ub = 1; }
-      }
-    }
-    out[i] = q;
-    if (out_lo) out_lo[i] = lb;
-    if (out_hi) out_hi[i] = ub;
-  }
-}
-
-__global__ void hq_kernel(double phi, const double* bv, const double* les,
-                          const uint64_t* goff, int64_t n_groups, int32_t n_grid,
-                          double* out, double* out_lo, double* out_hi) {
-  size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  size_t total = (size_t)n_groups * n_grid;
-  size_t stride = (size_t)gridDim.x * blockDim.x;
-  for (; i < total; i += stride) {
-    int64_t grp = (int64_t)(i / n_grid);
-    int32_t g = (int32_t)(i % n_grid);
-    int64_t lo = (int64_t)goff[grp];
-    int64_t n_les = (int64_t)(goff[grp + 1] - lo);
-    double q = vm_dnan(), lb = vm_dnan(), ub = vm_dnan();
-    if (!vm_isnan(phi)) {
-      double fix_prev = 0;
-      double v_last = 0;
-      for (int64_t j = 0; j < n_les; j++) {
-        double v = bv[(size_t)(lo + j) * n_grid + g];
-        if (j == 0) fix_prev = vm_isnan(v) ? 0 : v;
-        else if (!(vm_isnan(v) || fix_prev > v)) fix_prev = v;
-        v_last = fix_prev;
-      }
-      if (v_last != 0) {
-        if (phi < 0) {
-          q = -vm_dinf();
-          lb = -vm_dinf();
-          double v0 = bv[(size_t)lo * n_grid + g];
-          ub = vm_isnan(v0) ? 0 : v0;
-        } else if (phi > 1) {
-          q = vm_dinf();
-          lb = v_last;
-          ub = vm_dinf();
-        } else {
-          double v_req = v_last * phi;
-          double vp = 0, lep = 0;
-          fix_prev = 0;
-          bool done = false;
-          for (int64_t j = 0; j < n_les && !done; j++) {
-            double raw = bv[(size_t)(lo + j) * n_grid + g];
-            double v;
-            if (j == 0) v = vm_isnan(raw) ? 0 : raw;
-            else v = (vm_isnan(raw) || fix_prev > raw) ? fix_prev : raw;
-            fix_prev = v;
-            double le = les[lo + j];
-            if (v <= 0) {
-              lep = le;
-              continue;
-            }
-            if (v < v_req) {
-              vp = v;
-              lep = le;
-              continue;
-            }
-            if (isinf(le)) break;
-            if (v == vp) {
-              q = lep;
-              lb = lep;
-              ub = v;
-              done = true;
-              break;
-            }
-            q = lep + (le - lep) * (v_req - vp) / (v - vp);
-            lb = lep;
-            ub = le;
-            done = true;
-          }
-          if (!done) {
-            double vv = vm_dnan();
-            for (int64_t j = n_les - 1; j >= 0; j--) {
-              if (!isinf(les[lo + j])) {
-                vv = les[lo + j];
-                break;
-              }
-            }
-            q = vv;
-            lb = vv;
-            ub = vm_dinf();
-          }
-        }
-      }
-    }
-    out[i] = q;
-    if (out_lo) out_lo[i] = lb;
-    if (out_hi) out_hi[i] = ub;
-  }
-}
-
 /* ------------------------------------------------------------------ */
 /* launch dispatch: compile-time specialization for hot funcs         */
 /* ------------------------------------------------------------------ */
@@ -3137,6 +2575,9 @@ int vm_batch_cols_get(uint64_t handle, vm_batch_cols* out) {
   out->perm = b.perm.empty() ? nullptr : b.perm.data();
   out->hot = &b.hot;
   out->cvot = &b.cvot;
+  out->d_out = b.d_out;
+  out->last_rows = b.last_rows;
+  out->last_grid = b.last_grid;
   return 0;
 }
 void vm_ctx_events(hipEvent_t* ev_start, hipEvent_t* ev_stop) {
@@ -3146,26 +2587,6 @@ void vm_ctx_events(hipEvent_t* ev_start, hipEvent_t* ev_stop) {
 void vm_ctx_set_last_kernel_ms(double ms) { g_ctx.last_kernel_ms = ms; }
 
 namespace {
-
-int set_err(char* errbuf, size_t len, const char* msg) {
-  if (errbuf && len) {
-    snprintf(errbuf, len, "%s", msg);
-  }
-  return 1;
-}
-
-int hip_err(char* errbuf, size_t len, const char* what, hipError_t e) {
-  if (errbuf && len) {
-    snprintf(errbuf, len, "%s: %s", what, hipGetErrorString(e));
-  }
-  return 2;
-}
-
-#define HIP_TRY(expr, what)                              \
-  do {                                                   \
-    hipError_t _e = (expr);                              \
-    if (_e != hipSuccess) return hip_err(errbuf, errbuf_len, what, _e); \
-  } while (0)
 
 /* copy series perm[i] of the source CSR into dense row i of the new CSR */
 __global__ __launch_bounds__(BLOCK_THREADS) void relayout_kernel(
@@ -3216,56 +2637,49 @@ static int relayout_by_group(Batch& b, const int32_t* group_ids,
     return 0;
   }
   uint64_t total = offsets_orig[n_series];
-  int64_t* d_ts2 = nullptr;
-  double* d_vals2 = nullptr;
-  uint64_t* d_soff = nullptr;
-  uint64_t* d_doff = nullptr;
-  uint32_t* d_perm = nullptr;
-  HIP_TRY(vm_dev_malloc(&d_ts2, total * 8 + 16), "alloc relayout ts");
-  HIP_TRY(vm_dev_malloc(&d_vals2, total * 8 + 16), "alloc relayout vals");
-  HIP_TRY(vm_dev_malloc(&d_soff, (size_t)(n_series + 1) * 8), "alloc relayout soff");
-  HIP_TRY(vm_dev_malloc(&d_doff, (size_t)(n_series + 1) * 8), "alloc relayout doff");
-  HIP_TRY(vm_dev_malloc(&d_perm, (size_t)n_series * 4), "alloc relayout perm");
+  VmPoolBuf<int64_t> d_ts2;
+  VmPoolBuf<double> d_vals2;
+  VmPoolBuf<uint64_t> d_soff, d_doff;
+  VmPoolBuf<uint32_t> d_perm;
+  VM_HIP_TRY(d_ts2.alloc(total * 8 + 16), "alloc relayout ts");
+  VM_HIP_TRY(d_vals2.alloc(total * 8 + 16), "alloc relayout vals");
+  VM_HIP_TRY(d_soff.alloc((size_t)(n_series + 1) * 8), "alloc relayout soff");
+  VM_HIP_TRY(d_doff.alloc((size_t)(n_series + 1) * 8), "alloc relayout doff");
+  VM_HIP_TRY(d_perm.alloc((size_t)n_series * 4), "alloc relayout perm");
   hipStream_t st = g_ctx.stream;
-  HIP_TRY(hipMemcpyAsync(d_soff, offsets_orig, (size_t)(n_series + 1) * 8,
-                         hipMemcpyHostToDevice, st), "ul soff");
-  HIP_TRY(hipMemcpyAsync(d_doff, new_offsets.data(), (size_t)(n_series + 1) * 8,
-                         hipMemcpyHostToDevice, st), "ul doff");
-  HIP_TRY(hipMemcpyAsync(d_perm, perm.data(), (size_t)n_series * 4,
-                         hipMemcpyHostToDevice, st), "ul perm");
+  VM_HIP_TRY(hipMemcpyAsync(d_soff.p, offsets_orig, (size_t)(n_series + 1) * 8,
+                            hipMemcpyHostToDevice, st), "ul soff");
+  VM_HIP_TRY(hipMemcpyAsync(d_doff.p, new_offsets.data(), (size_t)(n_series + 1) * 8,
+                            hipMemcpyHostToDevice, st), "ul doff");
+  VM_HIP_TRY(hipMemcpyAsync(d_perm.p, perm.data(), (size_t)n_series * 4,
+                            hipMemcpyHostToDevice, st), "ul perm");
   uint32_t blocks = std::min<uint32_t>(
       (n_series + WAVES_PER_BLOCK - 1) / WAVES_PER_BLOCK, 4096);
   hipLaunchKernelGGL(relayout_kernel, dim3(blocks), dim3(BLOCK_THREADS), 0, st,
-                     b.d_ts, b.d_vals, d_soff, d_perm, d_doff, n_series,
-                     d_ts2, d_vals2);
-  HIP_TRY(hipStreamSynchronize(st), "sync relayout");
+                     b.d_ts, b.d_vals, d_soff.p, d_perm.p, d_doff.p, n_series,
+                     d_ts2.p, d_vals2.p);
+  VM_HIP_TRY(hipStreamSynchronize(st), "sync relayout");
   hipError_t kerr = hipGetLastError();
-  (void)vm_dev_free(d_soff);
-  (void)vm_dev_free(d_doff);
-  (void)vm_dev_free(d_perm);
-  if (kerr != hipSuccess) {
-    (void)vm_dev_free(d_ts2);
-    (void)vm_dev_free(d_vals2);
-    return hip_err(errbuf, errbuf_len, "relayout kernel", kerr);
-  }
+  if (kerr != hipSuccess)
+    return vm_hip_err(errbuf, errbuf_len, "relayout kernel", kerr);
   (void)vm_dev_free(b.d_ts);
   (void)vm_dev_free(b.d_vals);
-  b.d_ts = d_ts2;
-  b.d_vals = d_vals2;
+  b.d_ts = d_ts2.release();
+  b.d_vals = d_vals2.release();
   b.perm = std::move(perm);
   return 0;
 }
 
 int build_si_index(Batch& b, char* errbuf, size_t errbuf_len) {
-  HIP_TRY(vm_dev_malloc(&b.d_si, (size_t)b.n_series * 8), "alloc si index");
+  VM_HIP_TRY(vm_dev_malloc(&b.d_si, (size_t)b.n_series * 8), "alloc si index");
   uint32_t blocks = std::min<uint32_t>(
       (b.n_series + WAVES_PER_BLOCK - 1) / WAVES_PER_BLOCK, 4096);
   hipLaunchKernelGGL(si_prep_kernel, dim3(blocks), dim3(BLOCK_THREADS), 0,
                      g_ctx.stream, b.d_ts, b.d_offsets, b.n_series, b.d_si);
-  HIP_TRY(hipStreamSynchronize(g_ctx.stream), "sync si index");
+  VM_HIP_TRY(hipStreamSynchronize(g_ctx.stream), "sync si index");
   hipError_t kerr = hipGetLastError();
   if (kerr != hipSuccess)
-    return hip_err(errbuf, errbuf_len, "si index kernel", kerr);
+    return vm_hip_err(errbuf, errbuf_len, "si index kernel", kerr);
   return 0;
 }
 
@@ -3287,6 +2701,104 @@ void free_batch(Batch& b) {
   vm_hot_state_free(&b.hot);
   vm_cvot_state_free(&b.cvot);
   b = Batch();
+}
+
+/* Everything a batch needs beyond its columns.  b comes in with d_ts /
+ * d_vals on the device in the caller's series order, n_series, n_groups and
+ * n_samples set; offsets_orig[n_series + 1] is that CSR on the host.  A
+ * failure leaves b half built: build_batch cleans up. */
+int build_batch_parts(Batch& b, const uint64_t* offsets_orig,
+                      const int32_t* group_ids,
+                      char* errbuf, size_t errbuf_len) {
+  const uint32_t n_series = b.n_series;
+  /* grouped batches: physically relayout so each group's series are
+   * contiguous in HBM (see relayout_by_group).  eff_* describe the
+   * PHYSICAL CSR used by the kernels; offsets_orig stays as the caller
+   * has it. */
+  std::vector<uint64_t> phys_offsets;
+  std::vector<int32_t> phys_gids;
+  const uint64_t* eff_offsets = offsets_orig;
+  const int32_t* eff_gids = group_ids;
+  if (group_ids && b.n_groups > 0) {
+    int rrc = relayout_by_group(b, group_ids, offsets_orig, n_series,
+                                phys_offsets, errbuf, errbuf_len);
+    if (rrc != 0) return rrc;
+    eff_offsets = phys_offsets.data();
+    if (!b.perm.empty()) {
+      phys_gids.resize(n_series);
+      for (uint32_t i = 0; i < n_series; i++)
+        phys_gids[i] = group_ids[b.perm[i]];
+      eff_gids = phys_gids.data();
+    }
+  }
+
+  /* partition series by length (host pass over the physical offsets);
+   * vmgpu_rollup_exec sizes the wave and block kernels' LDS from the two
+   * maxima */
+  std::vector<uint32_t> wave_list, block_list, huge_list;
+  std::vector<uint64_t> huge_scr_off;
+  uint64_t huge_total = 0;
+  for (uint32_t s = 0; s < n_series; s++) {
+    uint64_t n = eff_offsets[s + 1] - eff_offsets[s];
+    if (n <= CHUNK_WAVE) {
+      wave_list.push_back(s);
+      if ((uint32_t)n > b.max_wave_len) b.max_wave_len = (uint32_t)n;
+    } else if (n <= CHUNK_BLOCK) {
+      block_list.push_back(s);
+      if ((uint32_t)n > b.max_block_len) b.max_block_len = (uint32_t)n;
+    } else {
+      huge_list.push_back(s);
+      huge_scr_off.push_back(huge_total);
+      huge_total += n;
+    }
+  }
+  b.n_wave = (uint32_t)wave_list.size();
+  b.n_block = (uint32_t)block_list.size();
+  b.n_huge = (uint32_t)huge_list.size();
+  b.wave_is_identity = (b.n_wave == n_series);
+  b.huge_scratch_elems = huge_total;
+
+  VM_HIP_TRY(vm_dev_malloc(&b.d_offsets, (n_series + 1) * sizeof(uint64_t)), "alloc offsets");
+  VM_HIP_TRY(hipMemcpy(b.d_offsets, eff_offsets, (n_series + 1) * sizeof(uint64_t), hipMemcpyHostToDevice), "upload offsets");
+  if (group_ids) {
+    VM_HIP_TRY(vm_dev_malloc(&b.d_group_ids, n_series * sizeof(int32_t)), "alloc gids");
+    VM_HIP_TRY(hipMemcpy(b.d_group_ids, eff_gids, n_series * sizeof(int32_t), hipMemcpyHostToDevice), "upload gids");
+  }
+  if (!b.wave_is_identity && b.n_wave) {
+    VM_HIP_TRY(vm_dev_malloc(&b.d_wave_list, b.n_wave * 4), "alloc wave list");
+    VM_HIP_TRY(hipMemcpy(b.d_wave_list, wave_list.data(), b.n_wave * 4, hipMemcpyHostToDevice), "upload wave list");
+  }
+  if (b.n_block) {
+    VM_HIP_TRY(vm_dev_malloc(&b.d_block_list, b.n_block * 4), "alloc block list");
+    VM_HIP_TRY(hipMemcpy(b.d_block_list, block_list.data(), b.n_block * 4, hipMemcpyHostToDevice), "upload block list");
+  }
+  if (b.n_huge) {
+    VM_HIP_TRY(vm_dev_malloc(&b.d_huge_list, b.n_huge * 4), "alloc huge list");
+    VM_HIP_TRY(hipMemcpy(b.d_huge_list, huge_list.data(), b.n_huge * 4, hipMemcpyHostToDevice), "upload huge list");
+    VM_HIP_TRY(vm_dev_malloc(&b.d_huge_scr_offsets, b.n_huge * 8), "alloc huge offsets");
+    VM_HIP_TRY(hipMemcpy(b.d_huge_scr_offsets, huge_scr_off.data(), b.n_huge * 8, hipMemcpyHostToDevice), "upload huge offsets");
+    VM_HIP_TRY(vm_dev_malloc(&b.d_scr_ts, huge_total * sizeof(int64_t)), "alloc scratch ts");
+    VM_HIP_TRY(vm_dev_malloc(&b.d_scr_vals, huge_total * sizeof(double)), "alloc scratch vals");
+  }
+  VM_HIP_TRY(vm_dev_malloc(&b.d_scanned, sizeof(unsigned long long)), "alloc scanned");
+  return build_si_index(b, errbuf, errbuf_len);
+}
+
+/* The one builder both create paths end in: completes b (see
+ * build_batch_parts) and registers it under a new handle.  On any failure
+ * the whole half-built batch is freed, the caller's columns included. */
+int build_batch(Batch& b, const uint64_t* offsets_orig,
+                const int32_t* group_ids, uint64_t* out_handle,
+                char* errbuf, size_t errbuf_len) {
+  int rc = build_batch_parts(b, offsets_orig, group_ids, errbuf, errbuf_len);
+  if (rc != 0) {
+    free_batch(b);
+    return rc;
+  }
+  uint64_t h = g_ctx.next_handle++;
+  g_ctx.batches[h] = b;
+  *out_handle = h;
+  return 0;
 }
 
 }  // namespace
@@ -3336,100 +2848,26 @@ int vmgpu_batch_create(const int64_t* ts, const double* vals,
                        uint64_t* out_handle,
                        char* errbuf, size_t errbuf_len) {
   std::lock_guard<std::mutex> lock(g_ctx.mu);
-  if (!g_ctx.inited) return set_err(errbuf, errbuf_len, "vmgpu: not initialized");
+  if (!g_ctx.inited) return vm_set_err(errbuf, errbuf_len, "vmgpu: not initialized");
   if (!ts || !vals || !offsets || !out_handle || n_series == 0)
-    return set_err(errbuf, errbuf_len, "vmgpu: bad args");
+    return vm_set_err(errbuf, errbuf_len, "vmgpu: bad args");
+  const uint64_t n_samples = offsets[n_series];
+  /* +16 B slack: the pipe kernel's clamped tail PAIR load may touch one
+   * element past the last series */
+  VmPoolBuf<int64_t> d_ts;
+  VmPoolBuf<double> d_vals;
+  VM_HIP_TRY(d_ts.alloc(n_samples * sizeof(int64_t) + 16), "alloc ts");
+  VM_HIP_TRY(d_vals.alloc(n_samples * sizeof(double) + 16), "alloc vals");
+  VM_HIP_TRY(hipMemcpy(d_ts.p, ts, n_samples * sizeof(int64_t), hipMemcpyHostToDevice), "upload ts");
+  VM_HIP_TRY(hipMemcpy(d_vals.p, vals, n_samples * sizeof(double), hipMemcpyHostToDevice), "upload vals");
+
   Batch b;
   b.n_series = n_series;
   b.n_groups = n_groups;
-  b.n_samples = offsets[n_series];
-
-  /* +16 B slack: the pipe kernel's clamped tail PAIR load may touch one
-   * element past the last series */
-  HIP_TRY(vm_dev_malloc(&b.d_ts, b.n_samples * sizeof(int64_t) + 16), "alloc ts");
-  HIP_TRY(vm_dev_malloc(&b.d_vals, b.n_samples * sizeof(double) + 16), "alloc vals");
-  HIP_TRY(hipMemcpy(b.d_ts, ts, b.n_samples * sizeof(int64_t), hipMemcpyHostToDevice), "upload ts");
-  HIP_TRY(hipMemcpy(b.d_vals, vals, b.n_samples * sizeof(double), hipMemcpyHostToDevice), "upload vals");
-
-  /* grouped batches: physically relayout so each group's series are
-   * contiguous in HBM (see relayout_by_group).  eff_* describe the
-   * PHYSICAL CSR used by the kernels. */
-  std::vector<uint64_t> phys_offsets;
-  std::vector<int32_t> phys_gids;
-  const uint64_t* eff_offsets = offsets;
-  const int32_t* eff_gids = group_ids;
-  if (group_ids && n_groups > 0) {
-    int rrc = relayout_by_group(b, group_ids, offsets, n_series,
-                                phys_offsets, errbuf, errbuf_len);
-    if (rrc != 0) {
-      free_batch(b);
-      return rrc;
-    }
-    eff_offsets = phys_offsets.data();
-    if (!b.perm.empty()) {
-      phys_gids.resize(n_series);
-      for (uint32_t i = 0; i < n_series; i++)
-        phys_gids[i] = group_ids[b.perm[i]];
-      eff_gids = phys_gids.data();
-    }
-  }
-
-  /* partition series by length (host pass over the physical offsets) */
-  std::vector<uint32_t> wave_list, block_list, huge_list;
-  std::vector<uint64_t> huge_scr_off;
-  uint64_t huge_total = 0;
-  for (uint32_t s = 0; s < n_series; s++) {
-    uint64_t n = eff_offsets[s + 1] - eff_offsets[s];
-    if (n <= CHUNK_WAVE) {
-      wave_list.push_back(s);
-      if ((uint32_t)n > b.max_wave_len) b.max_wave_len = (uint32_t)n;
-    } else if (n <= CHUNK_BLOCK) {
-      block_list.push_back(s);
-      if ((uint32_t)n > b.max_block_len) b.max_block_len = (uint32_t)n;
-    } else {
-      huge_list.push_back(s);
-      huge_scr_off.push_back(huge_total);
-      huge_total += n;
-    }
-  }
-  b.n_wave = (uint32_t)wave_list.size();
-  b.n_block = (uint32_t)block_list.size();
-  b.n_huge = (uint32_t)huge_list.size();
-  b.wave_is_identity = (b.n_wave == n_series);
-  b.huge_scratch_elems = huge_total;
-
-  HIP_TRY(vm_dev_malloc(&b.d_offsets, (n_series + 1) * sizeof(uint64_t)), "alloc offsets");
-  HIP_TRY(hipMemcpy(b.d_offsets, eff_offsets, (n_series + 1) * sizeof(uint64_t), hipMemcpyHostToDevice), "upload offsets");
-  if (group_ids) {
-    HIP_TRY(vm_dev_malloc(&b.d_group_ids, n_series * sizeof(int32_t)), "alloc gids");
-    HIP_TRY(hipMemcpy(b.d_group_ids, eff_gids, n_series * sizeof(int32_t), hipMemcpyHostToDevice), "upload gids");
-  }
-  if (!b.wave_is_identity && b.n_wave) {
-    HIP_TRY(vm_dev_malloc(&b.d_wave_list, b.n_wave * 4), "alloc wave list");
-    HIP_TRY(hipMemcpy(b.d_wave_list, wave_list.data(), b.n_wave * 4, hipMemcpyHostToDevice), "upload wave list");
-  }
-  if (b.n_block) {
-    HIP_TRY(vm_dev_malloc(&b.d_block_list, b.n_block * 4), "alloc block list");
-    HIP_TRY(hipMemcpy(b.d_block_list, block_list.data(), b.n_block * 4, hipMemcpyHostToDevice), "upload block list");
-  }
-  if (b.n_huge) {
-    HIP_TRY(vm_dev_malloc(&b.d_huge_list, b.n_huge * 4), "alloc huge list");
-    HIP_TRY(hipMemcpy(b.d_huge_list, huge_list.data(), b.n_huge * 4, hipMemcpyHostToDevice), "upload huge list");
-    HIP_TRY(vm_dev_malloc(&b.d_huge_scr_offsets, b.n_huge * 8), "alloc huge offsets");
-    HIP_TRY(hipMemcpy(b.d_huge_scr_offsets, huge_scr_off.data(), b.n_huge * 8, hipMemcpyHostToDevice), "upload huge offsets");
-    HIP_TRY(vm_dev_malloc(&b.d_scr_ts, huge_total * sizeof(int64_t)), "alloc scratch ts");
-    HIP_TRY(vm_dev_malloc(&b.d_scr_vals, huge_total * sizeof(double)), "alloc scratch vals");
-  }
-  HIP_TRY(vm_dev_malloc(&b.d_scanned, sizeof(unsigned long long)), "alloc scanned");
-  {
-    int src_rc = build_si_index(b, errbuf, errbuf_len);
-    if (src_rc != 0) { free_batch(b); return src_rc; }
-  }
-
-  uint64_t h = g_ctx.next_handle++;
-  g_ctx.batches[h] = b;
-  *out_handle = h;
-  return 0;
+  b.n_samples = n_samples;
+  b.d_ts = d_ts.release();
+  b.d_vals = d_vals.release();
+  return build_batch(b, offsets, group_ids, out_handle, errbuf, errbuf_len);
 }
 
 /* decode.hip seam: decode blocks, merge+dedup, compact — device-resident */
@@ -3453,9 +2891,9 @@ int vmgpu_batch_create_from_blocks(
     uint64_t* out_handle, uint64_t* out_offsets,
     char* errbuf, size_t errbuf_len) {
   std::lock_guard<std::mutex> lock(g_ctx.mu);
-  if (!g_ctx.inited) return set_err(errbuf, errbuf_len, "vmgpu: not initialized");
+  if (!g_ctx.inited) return vm_set_err(errbuf, errbuf_len, "vmgpu: not initialized");
   if (!out_handle || !out_offsets || n_series == 0)
-    return set_err(errbuf, errbuf_len, "vmgpu: bad args");
+    return vm_set_err(errbuf, errbuf_len, "vmgpu: bad args");
   int64_t* d_ts = nullptr;
   double* d_vals = nullptr;
   int rc = vmdec_decode_merge_device(payload, payload_len, blocks, n_blocks,
@@ -3471,97 +2909,8 @@ int vmgpu_batch_create_from_blocks(
   b.n_samples = out_offsets[n_series];
   b.d_ts = d_ts;
   b.d_vals = d_vals;
-
-  /* grouped: physically relayout (see relayout_by_group); out_offsets
-   * reported to the caller stay in ORIGINAL series order */
-  std::vector<uint64_t> phys_offsets;
-  std::vector<int32_t> phys_gids;
-  const uint64_t* eff_offsets = out_offsets;
-  const int32_t* eff_gids = group_ids;
-  if (group_ids && n_groups > 0) {
-    int rrc = relayout_by_group(b, group_ids, out_offsets, n_series,
-                                phys_offsets, errbuf, errbuf_len);
-    if (rrc != 0) {
-      free_batch(b);
-      return rrc;
-    }
-    eff_offsets = phys_offsets.data();
-    if (!b.perm.empty()) {
-      phys_gids.resize(n_series);
-      for (uint32_t i = 0; i < n_series; i++)
-        phys_gids[i] = group_ids[b.perm[i]];
-      eff_gids = phys_gids.data();
-    }
-  }
-
-  std::vector<uint32_t> wave_list, block_list, huge_list;
-  std::vector<uint64_t> huge_scr_off;
-  uint64_t huge_total = 0;
-  for (uint32_t s = 0; s < n_series; s++) {
-    uint64_t n = eff_offsets[s + 1] - eff_offsets[s];
-    if (n <= CHUNK_WAVE) {
-      wave_list.push_back(s);
-      if ((uint32_t)n > b.max_wave_len) b.max_wave_len = (uint32_t)n;
-    } else if (n <= CHUNK_BLOCK) {
-      block_list.push_back(s);
-    } else {
-      huge_list.push_back(s);
-      huge_scr_off.push_back(huge_total);
-      huge_total += n;
-    }
-  }
-  b.n_wave = (uint32_t)wave_list.size();
-  b.n_block = (uint32_t)block_list.size();
-  b.n_huge = (uint32_t)huge_list.size();
-  b.wave_is_identity = (b.n_wave == n_series);
-  b.huge_scratch_elems = huge_total;
-
-#define FBB_TRY(expr, what)                                                  \
-  do {                                                                       \
-    hipError_t _e = (expr);                                                  \
-    if (_e != hipSuccess) { free_batch(b);                                   \
-      return hip_err(errbuf, errbuf_len, what, _e); }                        \
-  } while (0)
-
-  FBB_TRY(vm_dev_malloc(&b.d_offsets, (n_series + 1) * sizeof(uint64_t)), "alloc offsets");
-  FBB_TRY(hipMemcpy(b.d_offsets, eff_offsets, (n_series + 1) * sizeof(uint64_t),
-                    hipMemcpyHostToDevice), "upload offsets");
-  if (group_ids) {
-    FBB_TRY(vm_dev_malloc(&b.d_group_ids, n_series * sizeof(int32_t)), "alloc gids");
-    FBB_TRY(hipMemcpy(b.d_group_ids, eff_gids, n_series * sizeof(int32_t),
-                      hipMemcpyHostToDevice), "upload gids");
-  }
-  if (!b.wave_is_identity && b.n_wave) {
-    FBB_TRY(vm_dev_malloc(&b.d_wave_list, b.n_wave * 4), "alloc wave list");
-    FBB_TRY(hipMemcpy(b.d_wave_list, wave_list.data(), b.n_wave * 4,
-                      hipMemcpyHostToDevice), "upload wave list");
-  }
-  if (b.n_block) {
-    FBB_TRY(vm_dev_malloc(&b.d_block_list, b.n_block * 4), "alloc block list");
-    FBB_TRY(hipMemcpy(b.d_block_list, block_list.data(), b.n_block * 4,
-                      hipMemcpyHostToDevice), "upload block list");
-  }
-  if (b.n_huge) {
-    FBB_TRY(vm_dev_malloc(&b.d_huge_list, b.n_huge * 4), "alloc huge list");
-    FBB_TRY(hipMemcpy(b.d_huge_list, huge_list.data(), b.n_huge * 4,
-                      hipMemcpyHostToDevice), "upload huge list");
-    FBB_TRY(vm_dev_malloc(&b.d_huge_scr_offsets, b.n_huge * 8), "alloc huge offsets");
-    FBB_TRY(hipMemcpy(b.d_huge_scr_offsets, huge_scr_off.data(), b.n_huge * 8,
-                      hipMemcpyHostToDevice), "upload huge offsets");
-    FBB_TRY(vm_dev_malloc(&b.d_scr_ts, huge_total * sizeof(int64_t)), "alloc scratch ts");
-    FBB_TRY(vm_dev_malloc(&b.d_scr_vals, huge_total * sizeof(double)), "alloc scratch vals");
-  }
-  FBB_TRY(vm_dev_malloc(&b.d_scanned, sizeof(unsigned long long)), "alloc scanned");
-#undef FBB_TRY
-  {
-    int src_rc = build_si_index(b, errbuf, errbuf_len);
-    if (src_rc != 0) { free_batch(b); return src_rc; }
-  }
-
-  uint64_t h = g_ctx.next_handle++;
-  g_ctx.batches[h] = b;
-  *out_handle = h;
-  return 0;
+  /* out_offsets reported to the caller stay in ORIGINAL series order */
+  return build_batch(b, out_offsets, group_ids, out_handle, errbuf, errbuf_len);
 }
 
 /* Native descriptor build from a packed block stream (vmgpu.h): the C
@@ -3577,13 +2926,13 @@ int vmgpu_batch_create_packed(
     char* errbuf, size_t errbuf_len) {
   if (!packed || !series_block_start || !out_handle || !out_offsets ||
       n_series == 0 || n_blocks == 0)
-    return set_err(errbuf, errbuf_len, "vmgpu: bad args");
+    return vm_set_err(errbuf, errbuf_len, "vmgpu: bad args");
   std::vector<vmgpu_block_desc> descs(n_blocks);
   uint64_t off = 0;
   uint64_t total_rows = 0;
   for (uint64_t i = 0; i < n_blocks; i++) {
     if (off + sizeof(vmgpu_packed_block_hdr) > packed_len)
-      return set_err(errbuf, errbuf_len, "vmgpu: packed stream truncated");
+      return vm_set_err(errbuf, errbuf_len, "vmgpu: packed stream truncated");
     vmgpu_packed_block_hdr h;
     memcpy(&h, packed + off, sizeof(h)); /* stream need not be aligned */
     off += sizeof(h);
@@ -3595,9 +2944,9 @@ int vmgpu_batch_create_packed(
     d.val_data_len = h.val_data_len;
     off += h.val_data_len;
     if (off > packed_len)
-      return set_err(errbuf, errbuf_len, "vmgpu: packed stream truncated");
+      return vm_set_err(errbuf, errbuf_len, "vmgpu: packed stream truncated");
     if (h.rows == 0 || h.rows > 8192)
-      return set_err(errbuf, errbuf_len, "vmgpu: bad packed rows");
+      return vm_set_err(errbuf, errbuf_len, "vmgpu: bad packed rows");
     d.out_off = total_rows;
     d.min_timestamp = h.min_timestamp;
     d.max_timestamp = h.max_timestamp;
@@ -3663,19 +3012,19 @@ int vmgpu_rollup_exec(const vmgpu_plan* plan, uint64_t handle,
                       uint64_t* out_samples_scanned,
                       char* errbuf, size_t errbuf_len) {
   std::lock_guard<std::mutex> lock(g_ctx.mu);
-  if (!g_ctx.inited) return set_err(errbuf, errbuf_len, "vmgpu: not initialized");
+  if (!g_ctx.inited) return vm_set_err(errbuf, errbuf_len, "vmgpu: not initialized");
   auto it = g_ctx.batches.find(handle);
-  if (it == g_ctx.batches.end()) return set_err(errbuf, errbuf_len, "vmgpu: bad handle");
+  if (it == g_ctx.batches.end()) return vm_set_err(errbuf, errbuf_len, "vmgpu: bad handle");
   Batch& b = it->second;
   if (plan->step <= 0 || plan->start > plan->end)
-    return set_err(errbuf, errbuf_len, "vmgpu: bad grid");
+    return vm_set_err(errbuf, errbuf_len, "vmgpu: bad grid");
   int64_t n_grid64 = 1 + (plan->end - plan->start) / plan->step;
   if (n_grid64 > (int64_t)1 << 30)
-    return set_err(errbuf, errbuf_len, "vmgpu: grid too large");
+    return vm_set_err(errbuf, errbuf_len, "vmgpu: grid too large");
   int32_t n_grid = (int32_t)n_grid64;
   bool grouped = plan->aggr != VMGPU_AGGR_NONE;
   if (grouped && (!b.d_group_ids || b.n_groups == 0))
-    return set_err(errbuf, errbuf_len, "vmgpu: aggr plan needs group_ids");
+    return vm_set_err(errbuf, errbuf_len, "vmgpu: aggr plan needs group_ids");
 
   size_t out_elems = grouped ? (size_t)b.n_groups * n_grid
                              : (size_t)b.n_series * n_grid;
@@ -3683,16 +3032,16 @@ int vmgpu_rollup_exec(const vmgpu_plan* plan, uint64_t handle,
   if (b.out_elems < out_elems) {
     (void)vm_dev_free(b.d_out);
     b.d_out = nullptr;
-    HIP_TRY(vm_dev_malloc(&b.d_out, out_elems * sizeof(double)), "alloc out");
+    VM_HIP_TRY(vm_dev_malloc(&b.d_out, out_elems * sizeof(double)), "alloc out");
     b.out_elems = out_elems;
   }
   if (count_elems && b.count_elems < count_elems) {
     (void)vm_dev_free(b.d_counts);
     b.d_counts = nullptr;
-    HIP_TRY(vm_dev_malloc(&b.d_counts, count_elems * sizeof(double)), "alloc counts");
+    VM_HIP_TRY(vm_dev_malloc(&b.d_counts, count_elems * sizeof(double)), "alloc counts");
     b.count_elems = count_elems;
   }
-  HIP_TRY(hipMemsetAsync(b.d_scanned, 0, 8, g_ctx.stream), "zero scanned");
+  VM_HIP_TRY(hipMemsetAsync(b.d_scanned, 0, 8, g_ctx.stream), "zero scanned");
 
   KPlan p;
   p.start = plan->start;
@@ -3784,7 +3133,7 @@ int vmgpu_rollup_exec(const vmgpu_plan* plan, uint64_t handle,
                        b.d_out, b.d_counts, n, plan->aggr);
   }
 
-  HIP_TRY(hipEventRecord(g_ctx.ev_start, g_ctx.stream), "event start");
+  VM_HIP_TRY(hipEventRecord(g_ctx.ev_start, g_ctx.stream), "event start");
 
   /* compile-time specializations for the hot functions (see launch_rollup) */
   if (b.n_wave) {
@@ -3820,7 +3169,7 @@ int vmgpu_rollup_exec(const vmgpu_plan* plan, uint64_t handle,
     launch_rollup(2, blocks, 0, p, w);
   }
 
-  HIP_TRY(hipEventRecord(g_ctx.ev_stop, g_ctx.stream), "event stop");
+  VM_HIP_TRY(hipEventRecord(g_ctx.ev_stop, g_ctx.stream), "event stop");
 
   if (grouped && !plan->skip_finalize) {
     uint64_t n = out_elems;
@@ -3830,22 +3179,22 @@ int vmgpu_rollup_exec(const vmgpu_plan* plan, uint64_t handle,
   }
 
   if (out) {
-    HIP_TRY(hipMemcpyAsync(out, b.d_out, out_elems * sizeof(double),
+    VM_HIP_TRY(hipMemcpyAsync(out, b.d_out, out_elems * sizeof(double),
                            hipMemcpyDeviceToHost, g_ctx.stream), "download out");
   }
   if (out_counts && count_elems) {
-    HIP_TRY(hipMemcpyAsync(out_counts, b.d_counts, count_elems * sizeof(double),
+    VM_HIP_TRY(hipMemcpyAsync(out_counts, b.d_counts, count_elems * sizeof(double),
                            hipMemcpyDeviceToHost, g_ctx.stream), "download counts");
   }
   unsigned long long scanned_h = 0;
-  HIP_TRY(hipMemcpyAsync(&scanned_h, b.d_scanned, 8, hipMemcpyDeviceToHost, g_ctx.stream),
+  VM_HIP_TRY(hipMemcpyAsync(&scanned_h, b.d_scanned, 8, hipMemcpyDeviceToHost, g_ctx.stream),
           "download scanned");
-  HIP_TRY(hipStreamSynchronize(g_ctx.stream), "sync");
+  VM_HIP_TRY(hipStreamSynchronize(g_ctx.stream), "sync");
   hipError_t kerr = hipGetLastError();
-  if (kerr != hipSuccess) return hip_err(errbuf, errbuf_len, "kernel", kerr);
+  if (kerr != hipSuccess) return vm_hip_err(errbuf, errbuf_len, "kernel", kerr);
 
   float ms = 0;
-  HIP_TRY(hipEventElapsedTime(&ms, g_ctx.ev_start, g_ctx.ev_stop), "event elapsed");
+  VM_HIP_TRY(hipEventElapsedTime(&ms, g_ctx.ev_start, g_ctx.ev_stop), "event elapsed");
   g_ctx.last_kernel_ms = (double)ms;
 
   if (out_samples_scanned) *out_samples_scanned = (uint64_t)scanned_h;
@@ -3919,321 +3268,6 @@ int vmgpu_rollup_eval(const vmgpu_plan* plan,
                          errbuf, errbuf_len);
   vmgpu_batch_destroy(h);
   return rc;
-}
-
-
-int vmgpu_topk_range(uint64_t handle, double k, int32_t summary_op,
-                     int32_t reverse, int64_t* out_sel, int64_t* out_n_sel,
-                     double* out_remaining, char* errbuf, size_t errbuf_len) {
-  std::lock_guard<std::mutex> lock(g_ctx.mu);
-  if (!g_ctx.inited) return set_err(errbuf, errbuf_len, "vmgpu: not initialized");
-  auto it = g_ctx.batches.find(handle);
-  if (it == g_ctx.batches.end()) return set_err(errbuf, errbuf_len, "vmgpu: bad handle");
-  Batch& b = it->second;
-  if (!b.d_out || b.last_rows == 0)
-    return set_err(errbuf, errbuf_len, "vmgpu: no evaluated output on this batch");
-  uint32_t n = b.last_rows;
-  int32_t n_grid = b.last_grid;
-  uint32_t kk = 0;
-  if (k == k && k > 0) kk = (k > (double)n) ? n : (uint32_t)k;
-  if (out_n_sel) *out_n_sel = 0;
-  if (kk == 0) return 0;
-
-  hipStream_t st = g_ctx.stream;
-  unsigned long long* d_keys = nullptr;
-  uint32_t* d_hist = nullptr;
-  uint32_t* d_misc = nullptr; /* counters */
-  uint32_t* d_sel = nullptr;
-  HIP_TRY(vm_dev_malloc(&d_keys, (size_t)n * 8), "alloc keys");
-  HIP_TRY(vm_dev_malloc(&d_hist, 65536 * 4), "alloc hist");
-  HIP_TRY(vm_dev_malloc(&d_misc, 8), "alloc counters");
-  HIP_TRY(vm_dev_malloc(&d_sel, (size_t)kk * 4), "alloc sel");
-  uint32_t blocks = std::min<uint32_t>((n + BLOCK_THREADS - 1) / BLOCK_THREADS * WAVES_PER_BLOCK, 2048);
-  hipLaunchKernelGGL(topk_summary_kernel, dim3(blocks), dim3(BLOCK_THREADS), 0, st,
-                     b.d_out, n, n_grid, summary_op, reverse, d_keys);
-  /* refine the k-th largest key threshold 16 bits at a time */
-  unsigned long long prefix = 0;
-  uint32_t need_above = kk; /* how many keys >= threshold so far required */
-  std::vector<uint32_t> hist(65536);
-  uint32_t above_total = 0;
-  for (int shift = 48; shift >= 0; shift -= 16) {
-    HIP_TRY(hipMemsetAsync(d_hist, 0, 65536 * 4, st), "zero hist");
-    uint32_t hblocks = std::min<uint32_t>((n + 255) / 256, 2048);
-    hipLaunchKernelGGL(topk_hist_kernel, dim3(hblocks), dim3(256), 0, st,
-                       d_keys, n, prefix, shift, d_hist);
-    HIP_TRY(hipMemcpyAsync(hist.data(), d_hist, 65536 * 4, hipMemcpyDeviceToHost, st), "dl hist");
-    HIP_TRY(hipStreamSynchronize(st), "sync hist");
-    uint32_t cum = 0;
-    int bin = 0;
-    for (int bb = 65535; bb >= 0; bb--) {
-      uint32_t c = hist[bb];
-      if (cum + c >= need_above - above_total) { bin = bb; break; }
-      cum += c;
-    }
-    above_total += cum;
-    prefix = (prefix << 16) | (unsigned long long)bin;
-  }
-  unsigned long long kstar = prefix;
-  uint32_t ties_quota = need_above - above_total;
-  HIP_TRY(hipMemsetAsync(d_misc, 0, 8, st), "zero counters");
-  uint32_t cblocks = std::min<uint32_t>((n + 255) / 256, 2048);
-  hipLaunchKernelGGL(topk_collect_kernel, dim3(cblocks), dim3(256), 0, st,
-                     d_keys, n, kstar, ties_quota, d_misc, d_sel, kk);
-  std::vector<uint32_t> sel(kk);
-  uint32_t nsel_h[2];
-  HIP_TRY(hipMemcpyAsync(sel.data(), d_sel, (size_t)kk * 4, hipMemcpyDeviceToHost, st), "dl sel");
-  HIP_TRY(hipMemcpyAsync(nsel_h, d_misc, 8, hipMemcpyDeviceToHost, st), "dl counters");
-  HIP_TRY(hipStreamSynchronize(st), "sync sel");
-  uint32_t m = std::min<uint32_t>(nsel_h[0], kk);
-  /* order the selection by key descending (reference output order after
-   * reverseSeries): download keys of the selected rows */
-  std::vector<unsigned long long> skeys(m);
-  for (uint32_t x = 0; x < m; x++) {
-    HIP_TRY(hipMemcpyAsync(&skeys[x], d_keys + sel[x], 8, hipMemcpyDeviceToHost, st), "dl key");
-  }
-  HIP_TRY(hipStreamSynchronize(st), "sync keys");
-  std::vector<uint32_t> order(m);
-  for (uint32_t x = 0; x < m; x++) order[x] = x;
-  std::sort(order.begin(), order.end(), [&](uint32_t a, uint32_t bx) {
-    if (skeys[a] != skeys[bx]) return skeys[a] > skeys[bx];
-    /* ties: descending row id, matching the oracle's reversed ascending
-     * sort (the reference's own sort is unstable: tie order unspecified) */
-    return sel[a] > sel[bx];
-  });
-  for (uint32_t x = 0; x < m; x++) out_sel[x] = (int64_t)sel[order[x]];
-  if (out_n_sel) *out_n_sel = (int64_t)m;
-
-  if (out_remaining) {
-    uint8_t* d_mask = nullptr;
-    double* d_rem = nullptr;
-    HIP_TRY(vm_dev_malloc(&d_mask, n), "alloc mask");
-    HIP_TRY(vm_dev_malloc(&d_rem, (size_t)n_grid * 16), "alloc rem");
-    HIP_TRY(hipMemsetAsync(d_mask, 0, n, st), "zero mask");
-    HIP_TRY(hipMemsetAsync(d_rem, 0, (size_t)n_grid * 16, st), "zero rem");
-    std::vector<uint8_t> mask(n, 0);
-    for (uint32_t x = 0; x < m; x++) mask[sel[x]] = 1;
-    HIP_TRY(hipMemcpyAsync(d_mask, mask.data(), n, hipMemcpyHostToDevice, st), "ul mask");
-    uint32_t rblocks = std::min<uint32_t>(
-        (uint32_t)(((size_t)n * n_grid + 255) / 256), 4096u);
-    hipLaunchKernelGGL(topk_remaining_kernel, dim3(rblocks), dim3(256), 0, st,
-                       b.d_out, n, n_grid, d_mask, d_rem, d_rem + n_grid);
-    std::vector<double> rem(2 * (size_t)n_grid);
-    HIP_TRY(hipMemcpyAsync(rem.data(), d_rem, (size_t)n_grid * 16, hipMemcpyDeviceToHost, st), "dl rem");
-    HIP_TRY(hipStreamSynchronize(st), "sync rem");
-    for (int32_t g = 0; g < n_grid; g++)
-      out_remaining[g] = (rem[n_grid + g] == 0) ? __builtin_nan("") : rem[g];
-    (void)vm_dev_free(d_mask);
-    (void)vm_dev_free(d_rem);
-  }
-  (void)vm_dev_free(d_keys);
-  (void)vm_dev_free(d_hist);
-  (void)vm_dev_free(d_misc);
-  (void)vm_dev_free(d_sel);
-  return 0;
-}
-
-int vmgpu_topk_pointwise(uint64_t handle, double k, int32_t reverse,
-                         double* out, char* errbuf, size_t errbuf_len) {
-  std::lock_guard<std::mutex> lock(g_ctx.mu);
-  if (!g_ctx.inited) return set_err(errbuf, errbuf_len, "vmgpu: not initialized");
-  auto it = g_ctx.batches.find(handle);
-  if (it == g_ctx.batches.end()) return set_err(errbuf, errbuf_len, "vmgpu: bad handle");
-  Batch& b = it->second;
-  if (!b.d_out || b.last_rows == 0)
-    return set_err(errbuf, errbuf_len, "vmgpu: no evaluated output on this batch");
-  uint32_t n = b.last_rows;
-  int32_t n_grid = b.last_grid;
-  uint32_t kk = 0;
-  if (k == k && k > 0) kk = (k > (double)n) ? n : (uint32_t)k;
-  hipStream_t st = g_ctx.stream;
-  if (kk >= n || n == 0) {
-    if (out) {
-      HIP_TRY(hipMemcpyAsync(out, b.d_out, (size_t)n * n_grid * 8,
-                             hipMemcpyDeviceToHost, st), "dl out");
-      HIP_TRY(hipStreamSynchronize(st), "sync");
-    }
-    return 0;
-  }
-  const uint32_t CAND_CAP = 8192;
-  uint32_t* d_hists = nullptr;
-  uint32_t* d_bins = nullptr;
-  unsigned long long* d_cand = nullptr;
-  unsigned long long* d_kstar = nullptr;
-  uint32_t* d_small = nullptr; /* cand_n[n_grid], ties[n_grid], taken[n_grid], overflow */
-  HIP_TRY(vm_dev_malloc(&d_hists, (size_t)n_grid * 65536 * 4), "alloc col hists");
-  HIP_TRY(vm_dev_malloc(&d_bins, (size_t)n_grid * 8), "alloc bins");
-  HIP_TRY(vm_dev_malloc(&d_cand, (size_t)n_grid * CAND_CAP * 8), "alloc cands");
-  HIP_TRY(vm_dev_malloc(&d_kstar, (size_t)n_grid * 8), "alloc kstar");
-  HIP_TRY(vm_dev_malloc(&d_small, (size_t)n_grid * 12 + 4), "alloc small");
-  uint32_t* d_cand_n = d_small;
-  uint32_t* d_ties = d_small + n_grid;
-  uint32_t* d_taken = d_small + 2 * (size_t)n_grid;
-  uint32_t* d_overflow = d_small + 3 * (size_t)n_grid;
-  HIP_TRY(hipMemsetAsync(d_hists, 0, (size_t)n_grid * 65536 * 4, st), "zero hists");
-  HIP_TRY(hipMemsetAsync(d_small, 0, (size_t)n_grid * 12 + 4, st), "zero small");
-  size_t total = (size_t)n * n_grid;
-  uint32_t eblocks = (uint32_t)std::min<size_t>((total + 255) / 256, 4096);
-  hipLaunchKernelGGL(topk_col_hist_kernel, dim3(eblocks), dim3(256), 0, st,
-                     b.d_out, n, n_grid, reverse, d_hists);
-  hipLaunchKernelGGL(topk_col_threshold_kernel,
-                     dim3((n_grid + 255) / 256), dim3(256), 0, st,
-                     d_hists, n_grid, kk, d_bins, d_bins + n_grid);
-  hipLaunchKernelGGL(topk_col_candidates_kernel, dim3(eblocks), dim3(256), 0, st,
-                     b.d_out, n, n_grid, reverse, d_bins, d_cand, d_cand_n,
-                     CAND_CAP, d_overflow);
-  uint32_t overflow_h = 0;
-  HIP_TRY(hipMemcpyAsync(&overflow_h, d_overflow, 4, hipMemcpyDeviceToHost, st), "dl ovf");
-  HIP_TRY(hipStreamSynchronize(st), "sync ovf");
-  if (overflow_h) {
-    (void)vm_dev_free(d_hists); (void)vm_dev_free(d_bins); (void)vm_dev_free(d_cand);
-    (void)vm_dev_free(d_kstar); (void)vm_dev_free(d_small);
-    return set_err(errbuf, errbuf_len,
-                   "vmgpu: topk candidate overflow (massive ties); unsupported");
-  }
-  hipLaunchKernelGGL(topk_col_kstar_kernel, dim3(n_grid), dim3(256), 0, st,
-                     d_cand, d_cand_n, CAND_CAP, d_bins + n_grid, kk, n_grid,
-                     d_kstar, d_ties);
-  hipLaunchKernelGGL(topk_col_fill_kernel, dim3(eblocks), dim3(256), 0, st,
-                     b.d_out, n, n_grid, reverse, kk, d_bins, d_kstar, d_taken,
-                     d_ties);
-  if (out) {
-    HIP_TRY(hipMemcpyAsync(out, b.d_out, total * 8, hipMemcpyDeviceToHost, st), "dl out");
-  }
-  HIP_TRY(hipStreamSynchronize(st), "sync fill");
-  hipError_t kerr = hipGetLastError();
-  (void)vm_dev_free(d_hists); (void)vm_dev_free(d_bins); (void)vm_dev_free(d_cand);
-  (void)vm_dev_free(d_kstar); (void)vm_dev_free(d_small);
-  if (kerr != hipSuccess) return hip_err(errbuf, errbuf_len, "topk kernel", kerr);
-  return 0;
-}
-
-int vmgpu_histogram_stat(int32_t mode, const double* bucket_values,
-                         const double* les, const uint64_t* group_offsets,
-                         uint32_t n_groups, int32_t n_grid, double* out,
-                         char* errbuf, size_t errbuf_len) {
-  std::lock_guard<std::mutex> lock(g_ctx.mu);
-  if (!g_ctx.inited) return set_err(errbuf, errbuf_len, "vmgpu: not initialized");
-  if (!bucket_values || !les || !group_offsets || !out || n_groups == 0 || n_grid <= 0)
-    return set_err(errbuf, errbuf_len, "vmgpu: bad args");
-  hipStream_t st = g_ctx.stream;
-  uint64_t n_rows = group_offsets[n_groups];
-  double* d_bv = nullptr;
-  double* d_les = nullptr;
-  uint64_t* d_off = nullptr;
-  double* d_out = nullptr;
-  size_t out_elems = (size_t)n_groups * n_grid;
-  HIP_TRY(vm_dev_malloc(&d_bv, (size_t)n_rows * n_grid * 8), "alloc bv");
-  HIP_TRY(vm_dev_malloc(&d_les, (size_t)n_rows * 8), "alloc les");
-  HIP_TRY(vm_dev_malloc(&d_off, (size_t)(n_groups + 1) * 8), "alloc off");
-  HIP_TRY(vm_dev_malloc(&d_out, out_elems * 8), "alloc out");
-  HIP_TRY(hipMemcpyAsync(d_bv, bucket_values, (size_t)n_rows * n_grid * 8,
-                         hipMemcpyHostToDevice, st), "ul bv");
-  HIP_TRY(hipMemcpyAsync(d_les, les, (size_t)n_rows * 8, hipMemcpyHostToDevice, st), "ul les");
-  HIP_TRY(hipMemcpyAsync(d_off, group_offsets, (size_t)(n_groups + 1) * 8,
-                         hipMemcpyHostToDevice, st), "ul off");
-  uint32_t blocks = (uint32_t)std::min<size_t>((out_elems + 255) / 256, 4096);
-  hipLaunchKernelGGL(hstat_kernel, dim3(blocks), dim3(256), 0, st, mode, d_bv,
-                     d_les, d_off, (int64_t)n_groups, n_grid, d_out);
-  HIP_TRY(hipMemcpyAsync(out, d_out, out_elems * 8, hipMemcpyDeviceToHost, st), "dl out");
-  HIP_TRY(hipStreamSynchronize(st), "sync hstat");
-  hipError_t kerr = hipGetLastError();
-  (void)vm_dev_free(d_bv); (void)vm_dev_free(d_les); (void)vm_dev_free(d_off);
-  (void)vm_dev_free(d_out);
-  if (kerr != hipSuccess) return hip_err(errbuf, errbuf_len, "hstat kernel", kerr);
-  return 0;
-}
-
-int vmgpu_histogram_share(const double* le_req, const double* bucket_values,
-                          const double* les, const uint64_t* group_offsets,
-                          uint32_t n_groups, int32_t n_grid, double* out,
-                          double* out_lower, double* out_upper,
-                          char* errbuf, size_t errbuf_len) {
-  std::lock_guard<std::mutex> lock(g_ctx.mu);
-  if (!g_ctx.inited) return set_err(errbuf, errbuf_len, "vmgpu: not initialized");
-  if (!le_req || !bucket_values || !les || !group_offsets || !out ||
-      n_groups == 0 || n_grid <= 0)
-    return set_err(errbuf, errbuf_len, "vmgpu: bad args");
-  hipStream_t st = g_ctx.stream;
-  uint64_t n_rows = group_offsets[n_groups];
-  double* d_req = nullptr;
-  double* d_bv = nullptr;
-  double* d_les = nullptr;
-  uint64_t* d_off = nullptr;
-  double* d_out = nullptr;
-  double* d_lo = nullptr;
-  double* d_hi = nullptr;
-  size_t out_elems = (size_t)n_groups * n_grid;
-  HIP_TRY(vm_dev_malloc(&d_req, (size_t)n_grid * 8), "alloc req");
-  HIP_TRY(vm_dev_malloc(&d_bv, (size_t)n_rows * n_grid * 8), "alloc bv");
-  HIP_TRY(vm_dev_malloc(&d_les, (size_t)n_rows * 8), "alloc les");
-  HIP_TRY(vm_dev_malloc(&d_off, (size_t)(n_groups + 1) * 8), "alloc off");
-  HIP_TRY(vm_dev_malloc(&d_out, out_elems * 8), "alloc out");
-  if (out_lower) HIP_TRY(vm_dev_malloc(&d_lo, out_elems * 8), "alloc lo");
-  if (out_upper) HIP_TRY(vm_dev_malloc(&d_hi, out_elems * 8), "alloc hi");
-  HIP_TRY(hipMemcpyAsync(d_req, le_req, (size_t)n_grid * 8,
-                         hipMemcpyHostToDevice, st), "ul req");
-  HIP_TRY(hipMemcpyAsync(d_bv, bucket_values, (size_t)n_rows * n_grid * 8,
-                         hipMemcpyHostToDevice, st), "ul bv");
-  HIP_TRY(hipMemcpyAsync(d_les, les, (size_t)n_rows * 8, hipMemcpyHostToDevice, st), "ul les");
-  HIP_TRY(hipMemcpyAsync(d_off, group_offsets, (size_t)(n_groups + 1) * 8,
-                         hipMemcpyHostToDevice, st), "ul off");
-  uint32_t blocks = (uint32_t)std::min<size_t>((out_elems + 255) / 256, 4096);
-  hipLaunchKernelGGL(hshare_kernel, dim3(blocks), dim3(256), 0, st, d_req,
-                     d_bv, d_les, d_off, (int64_t)n_groups, n_grid,
-                     d_out, d_lo, d_hi);
-  HIP_TRY(hipMemcpyAsync(out, d_out, out_elems * 8, hipMemcpyDeviceToHost, st), "dl out");
-  if (out_lower) HIP_TRY(hipMemcpyAsync(out_lower, d_lo, out_elems * 8, hipMemcpyDeviceToHost, st), "dl lo");
-  if (out_upper) HIP_TRY(hipMemcpyAsync(out_upper, d_hi, out_elems * 8, hipMemcpyDeviceToHost, st), "dl hi");
-  HIP_TRY(hipStreamSynchronize(st), "sync hshare");
-  hipError_t kerr = hipGetLastError();
-  (void)vm_dev_free(d_req); (void)vm_dev_free(d_bv); (void)vm_dev_free(d_les);
-  (void)vm_dev_free(d_off); (void)vm_dev_free(d_out); (void)vm_dev_free(d_lo);
-  (void)vm_dev_free(d_hi);
-  if (kerr != hipSuccess) return hip_err(errbuf, errbuf_len, "hshare kernel", kerr);
-  return 0;
-}
-
-int vmgpu_histogram_quantile(double phi, const double* bucket_values,
-                             const double* les, const uint64_t* group_offsets,
-                             uint32_t n_groups, int32_t n_grid,
-                             double* out, double* out_lower, double* out_upper,
-                             char* errbuf, size_t errbuf_len) {
-  std::lock_guard<std::mutex> lock(g_ctx.mu);
-  if (!g_ctx.inited) return set_err(errbuf, errbuf_len, "vmgpu: not initialized");
-  if (!bucket_values || !les || !group_offsets || !out || n_groups == 0 || n_grid <= 0)
-    return set_err(errbuf, errbuf_len, "vmgpu: bad args");
-  hipStream_t st = g_ctx.stream;
-  uint64_t n_rows = group_offsets[n_groups];
-  double* d_bv = nullptr;
-  double* d_les = nullptr;
-  uint64_t* d_off = nullptr;
-  double* d_out = nullptr;
-  double* d_lo = nullptr;
-  double* d_hi = nullptr;
-  size_t out_elems = (size_t)n_groups * n_grid;
-  HIP_TRY(vm_dev_malloc(&d_bv, (size_t)n_rows * n_grid * 8), "alloc bv");
-  HIP_TRY(vm_dev_malloc(&d_les, (size_t)n_rows * 8), "alloc les");
-  HIP_TRY(vm_dev_malloc(&d_off, (size_t)(n_groups + 1) * 8), "alloc off");
-  HIP_TRY(vm_dev_malloc(&d_out, out_elems * 8), "alloc out");
-  if (out_lower) HIP_TRY(vm_dev_malloc(&d_lo, out_elems * 8), "alloc lo");
-  if (out_upper) HIP_TRY(vm_dev_malloc(&d_hi, out_elems * 8), "alloc hi");
-  HIP_TRY(hipMemcpyAsync(d_bv, bucket_values, (size_t)n_rows * n_grid * 8,
-                         hipMemcpyHostToDevice, st), "ul bv");
-  HIP_TRY(hipMemcpyAsync(d_les, les, (size_t)n_rows * 8, hipMemcpyHostToDevice, st), "ul les");
-  HIP_TRY(hipMemcpyAsync(d_off, group_offsets, (size_t)(n_groups + 1) * 8,
-                         hipMemcpyHostToDevice, st), "ul off");
-  uint32_t blocks = (uint32_t)std::min<size_t>((out_elems + 255) / 256, 4096);
-  hipLaunchKernelGGL(hq_kernel, dim3(blocks), dim3(256), 0, st, phi, d_bv, d_les,
-                     d_off, (int64_t)n_groups, n_grid, d_out, d_lo, d_hi);
-  HIP_TRY(hipMemcpyAsync(out, d_out, out_elems * 8, hipMemcpyDeviceToHost, st), "dl out");
-  if (out_lower) HIP_TRY(hipMemcpyAsync(out_lower, d_lo, out_elems * 8, hipMemcpyDeviceToHost, st), "dl lo");
-  if (out_upper) HIP_TRY(hipMemcpyAsync(out_upper, d_hi, out_elems * 8, hipMemcpyDeviceToHost, st), "dl hi");
-  HIP_TRY(hipStreamSynchronize(st), "sync hq");
-  hipError_t kerr = hipGetLastError();
-  (void)vm_dev_free(d_bv); (void)vm_dev_free(d_les); (void)vm_dev_free(d_off);
-  (void)vm_dev_free(d_out); (void)vm_dev_free(d_lo); (void)vm_dev_free(d_hi);
-  if (kerr != hipSuccess) return hip_err(errbuf, errbuf_len, "hq kernel", kerr);
-  return 0;
 }
 
 int vmgpu_last_kernel_ms(double* out_ms) {
