@@ -137,7 +137,14 @@ int vmgpu_rollup_eval(const vmgpu_plan* plan,
  *   0=avg 1=min 2=max 3=median 4=last), returns up to k row ids in the
  *   reference's output order and optionally the per-point remaining sum.
  * vmgpu_topk_pointwise: per-grid-point top/bottom-k across rows; all other
- *   values become NaN (fillNaNsAtIdx); out may be NULL to keep on device. */
+ *   values become NaN (fillNaNsAtIdx); out may be NULL to keep on device.
+ *   Any number of equal or near-equal values in a column is supported.
+ * Both work on PHYSICAL rows: on a batch created with group_ids the rows
+ * are relayouted by group, so out_sel holds physical row ids and out is in
+ * physical row order.  vmgpu_batch_perm maps them: physical row i is
+ * original series perm[i].  Of several rows tied at the boundary, which
+ * ones are kept is unspecified (the reference's sort is unstable); rows of
+ * equal summary come out of vmgpu_topk_range in descending physical id. */
 int vmgpu_topk_range(uint64_t handle, double k, int32_t summary_op,
                      int32_t reverse, int64_t* out_sel, int64_t* out_n_sel,
                      double* out_remaining, char* errbuf, size_t errbuf_len);

@@ -5,9 +5,9 @@
  *       twins: one summary key per series row, then the k-th largest key by
  *       16-bit histogram refinement; the optional "remaining sum" row adds
  *       up what was not selected.
- *   vmgpu_topk_pointwise  topk / bottomk: per grid column, the boundary bin
- *       of a 65536-bin histogram, then the exact k-th largest key among that
- *       bin's candidates; what lies below it is set to NaN in place.
+ *   vmgpu_topk_pointwise  topk / bottomk: per grid column, the k-th largest
+ *       key by the same 16-bit histogram refinement, one 65536-bin histogram
+ *       per column and round; what lies below it is set to NaN in place.
  *
  * Reaches the batch through batch_access.h and runs on the context stream
  * under the context lock, like hot.hip.
@@ -242,145 +242,108 @@ __global__ void topk_remaining_kernel(const double* values, uint32_t n_series,
 
 /* ---- pointwise topk over [n_series x n_grid] ---- */
 
+/* One refinement round: per column, the 16-bit histogram of the key bits at
+ * shift, over the keys whose bits above shift+16 equal the column's prefix
+ * (every key in the first round, shift 48). */
 __global__ void topk_col_hist_kernel(const double* values, uint32_t n_series,
                                      int32_t n_grid, int32_t reverse,
-                                     uint32_t* hists) {
+                                     const unsigned long long* prefix_of_col,
+                                     int shift, uint32_t* hists) {
   size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   size_t total = (size_t)n_series * n_grid;
   size_t stride = (size_t)gridDim.x * blockDim.x;
   for (; i < total; i += stride) {
     int32_t g = (int32_t)(i % n_grid);
     unsigned long long k = vm_topk_key(values[i], reverse);
-    atomicAdd(&hists[(size_t)g * 65536 + (k >> 48)], 1u);
+    if (shift < 48 && (k >> (shift + 16)) != prefix_of_col[g]) continue;
+    atomicAdd(&hists[(size_t)g * 65536 + ((k >> shift) & 0xffff)], 1u);
   }
 }
 
-__global__ void topk_col_threshold_kernel(const uint32_t* hists, int32_t n_grid,
-                                          uint32_t k, uint32_t* bin_of_col,
-                                          uint32_t* above_of_col) {
-  int g = blockIdx.x * blockDim.x + threadIdx.x;
-  if (g >= n_grid) return;
-  const uint32_t* h = hists + (size_t)g * 65536;
-  uint32_t cum = 0;
-  int bin = 0;
-  for (int b = 65535; b >= 0; b--) {
-    uint32_t c = h[b];
-    if (cum + c >= k) {
-      bin = b;
-      break;
-    }
-    cum += c;
-  }
-  bin_of_col[g] = (uint32_t)bin;
-  above_of_col[g] = cum;
-}
-
-__global__ void topk_col_candidates_kernel(const double* values, uint32_t n_series,
-                                           int32_t n_grid, int32_t reverse,
-                                           const uint32_t* bin_of_col,
-                                           unsigned long long* cand,
-                                           uint32_t* cand_n, uint32_t cap,
-                                           uint32_t* overflow) {
-  size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  size_t total = (size_t)n_series * n_grid;
-  size_t stride = (size_t)gridDim.x * blockDim.x;
-  for (; i < total; i += stride) {
-    int32_t g = (int32_t)(i % n_grid);
-    unsigned long long k = vm_topk_key(values[i], reverse);
-    if ((uint32_t)(k >> 48) != bin_of_col[g]) continue;
-    uint32_t slot = atomicAdd(&cand_n[g], 1u);
-    if (slot < cap) cand[(size_t)g * cap + slot] = k;
-    else atomicAdd(overflow, 1u);
-  }
-}
-
-__global__ __launch_bounds__(256) void topk_col_kstar_kernel(
-    const unsigned long long* cand, const uint32_t* cand_n, uint32_t cap,
-    const uint32_t* above_of_col, uint32_t k, int32_t n_grid,
-    unsigned long long* kstar_of_col, uint32_t* ties_of_col) {
+/* One block per column: walks the column's histogram from the top bin down
+ * to the bin that holds the need-th largest key still in play, appends that
+ * bin to the column's prefix and takes the keys above it off the need.
+ * After the fourth round the prefix is the k-th largest key of the column
+ * and the need is how many keys equal to it are kept.  k0 seeds the need in
+ * the first round (first != 0). */
+__global__ __launch_bounds__(BLOCK_THREADS) void topk_col_refine_kernel(
+    const uint32_t* hists, int32_t n_grid, uint32_t k0, int32_t first,
+    unsigned long long* prefix_of_col, uint32_t* need_of_col) {
   int g = blockIdx.x;
   if (g >= n_grid) return;
-  uint32_t n = cand_n[g];
-  if (n > cap) n = cap;
-  uint32_t need = k > above_of_col[g] ? k - above_of_col[g] : 0;
-  const unsigned long long* c = cand + (size_t)g * cap;
-  __shared__ unsigned long long sh_lo, sh_hi, sh_mid;
-  __shared__ uint32_t sh_cnt;
-  if (threadIdx.x == 0) {
-    sh_lo = 0;
-    sh_hi = ~0ULL;
+  const uint32_t* h = hists + (size_t)g * 65536;
+  /* sh_sum[c]: total of the 256 bins [c*256, c*256+256) */
+  __shared__ uint32_t sh_sum[BLOCK_THREADS];
+  __shared__ uint32_t sh_bin[BLOCK_THREADS];
+  __shared__ uint32_t sh_chunk, sh_cum;
+  const int t = threadIdx.x;
+  sh_sum[t] = 0;
+  __syncthreads();
+  for (int c = 0; c < 256; c++) {
+    uint32_t v = h[c * 256 + t];
+    if (v) atomicAdd(&sh_sum[c], v);
   }
   __syncthreads();
-  if (need == 0 || n == 0) {
-    if (threadIdx.x == 0) {
-      kstar_of_col[g] = ~0ULL;
-      ties_of_col[g] = 0;
+  const uint32_t need = first ? k0 : need_of_col[g];
+  if (t == 0) {
+    uint32_t cum = 0;
+    int chunk = 0;
+    for (int c = 255; c >= 0; c--) {
+      uint32_t s = sh_sum[c];
+      if (cum + s >= need) {
+        chunk = c;
+        break;
+      }
+      cum += s;
     }
-    return;
+    sh_chunk = (uint32_t)chunk;
+    sh_cum = cum;
   }
-  for (int it = 0; it < 64; it++) {
-    if (threadIdx.x == 0) {
-      sh_mid = sh_lo + ((sh_hi - sh_lo) >> 1);
-      sh_cnt = 0;
-    }
-    __syncthreads();
-    unsigned long long mid = sh_mid;
-    uint32_t local = 0;
-    for (uint32_t t = threadIdx.x; t < n; t += blockDim.x)
-      if (c[t] >= mid) local++;
-    atomicAdd(&sh_cnt, local);
-    __syncthreads();
-    bool done = false;
-    if (threadIdx.x == 0) {
-      if (sh_cnt >= need) sh_lo = sh_mid + 1;
-      else sh_hi = sh_mid;
-    }
-    __syncthreads();
-    if (sh_lo >= sh_hi) { done = true; }
-    if (done) break;
-  }
-  unsigned long long kstar = sh_lo - 1;
-  if (threadIdx.x == 0) sh_cnt = 0;
   __syncthreads();
-  uint32_t local = 0;
-  for (uint32_t t = threadIdx.x; t < n; t += blockDim.x)
-    if (c[t] > kstar) local++;
-  atomicAdd(&sh_cnt, local);
+  sh_bin[t] = h[sh_chunk * 256 + t];
   __syncthreads();
-  if (threadIdx.x == 0) {
-    kstar_of_col[g] = kstar;
-    ties_of_col[g] = need - sh_cnt;
+  if (t == 0) {
+    uint32_t cum = sh_cum;
+    int bin = 0;
+    for (int b = 255; b >= 0; b--) {
+      uint32_t c = sh_bin[b];
+      if (cum + c >= need) {
+        bin = b;
+        break;
+      }
+      cum += c;
+    }
+    unsigned long long prefix = first ? 0ULL : prefix_of_col[g];
+    prefix_of_col[g] = (prefix << 16) | (unsigned long long)(sh_chunk * 256 + bin);
+    need_of_col[g] = need - cum;
   }
 }
 
+/* NaN-fills what lies below the column's k-th largest key; of the keys equal
+ * to it, the first ties_of_col[g] to arrive stay (the reference's sort is
+ * unstable: which of several equal boundary values survives is unspecified
+ * there too). */
 __global__ void topk_col_fill_kernel(double* values, uint32_t n_series,
-                                     int32_t n_grid, int32_t reverse, uint32_t k,
-                                     const uint32_t* bin_of_col,
+                                     int32_t n_grid, int32_t reverse,
                                      const unsigned long long* kstar_of_col,
-                                     uint32_t* ties_taken,
-                                     const uint32_t* ties_of_col) {
+                                     const uint32_t* ties_of_col,
+                                     uint32_t* ties_taken) {
   size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   size_t total = (size_t)n_series * n_grid;
   size_t stride = (size_t)gridDim.x * blockDim.x;
   for (; i < total; i += stride) {
     int32_t g = (int32_t)(i % n_grid);
     unsigned long long key = vm_topk_key(values[i], reverse);
-    uint32_t bin = bin_of_col[g];
-    uint32_t kb = (uint32_t)(key >> 48);
+    if (key == 0) continue; /* NaN stays NaN whether kept or not */
+    unsigned long long kstar = kstar_of_col[g];
     bool keep;
-    if (kb > bin) {
+    if (key > kstar) {
       keep = true;
-    } else if (kb < bin) {
-      keep = false;
+    } else if (key == kstar) {
+      uint32_t t = atomicAdd(&ties_taken[g], 1u);
+      keep = t < ties_of_col[g];
     } else {
-      unsigned long long kstar = kstar_of_col[g];
-      if (key > kstar) keep = true;
-      else if (key == kstar) {
-        uint32_t t = atomicAdd(&ties_taken[g], 1u);
-        keep = t < ties_of_col[g];
-      } else {
-        keep = false;
-      }
+      keep = false;
     }
     if (!keep) values[i] = vm_dnan();
   }
@@ -518,47 +481,30 @@ int vmgpu_topk_pointwise(uint64_t handle, double k, int32_t reverse,
     }
     return 0;
   }
-  const uint32_t CAND_CAP = 8192;
-  VmPoolBuf<uint32_t> hists_buf, bins_buf, small_buf;
-  VmPoolBuf<unsigned long long> cand_buf, kstar_buf;
+  /* the k-th largest key of every column, 16 bits per round: five scans of
+   * the matrix in all, for any number of equal or near-equal values */
+  VmPoolBuf<uint32_t> hists_buf, small_buf;
+  VmPoolBuf<unsigned long long> kstar_buf;
   VM_HIP_TRY(hists_buf.alloc((size_t)n_grid * 65536 * 4), "alloc col hists");
-  VM_HIP_TRY(bins_buf.alloc((size_t)n_grid * 8), "alloc bins");
-  VM_HIP_TRY(cand_buf.alloc((size_t)n_grid * CAND_CAP * 8), "alloc cands");
   VM_HIP_TRY(kstar_buf.alloc((size_t)n_grid * 8), "alloc kstar");
-  VM_HIP_TRY(small_buf.alloc((size_t)n_grid * 12 + 4), "alloc small");
+  VM_HIP_TRY(small_buf.alloc((size_t)n_grid * 8), "alloc small");
   uint32_t* d_hists = hists_buf.p;
-  uint32_t* d_bins = bins_buf.p;
-  unsigned long long* d_cand = cand_buf.p;
-  unsigned long long* d_kstar = kstar_buf.p;
-  uint32_t* d_small = small_buf.p; /* cand_n[n_grid], ties[n_grid], taken[n_grid], overflow */
-  uint32_t* d_cand_n = d_small;
-  uint32_t* d_ties = d_small + n_grid;
-  uint32_t* d_taken = d_small + 2 * (size_t)n_grid;
-  uint32_t* d_overflow = d_small + 3 * (size_t)n_grid;
-  VM_HIP_TRY(hipMemsetAsync(d_hists, 0, (size_t)n_grid * 65536 * 4, st), "zero hists");
-  VM_HIP_TRY(hipMemsetAsync(d_small, 0, (size_t)n_grid * 12 + 4, st), "zero small");
+  unsigned long long* d_kstar = kstar_buf.p; /* prefix while refining */
+  uint32_t* d_need = small_buf.p;            /* ties to keep, at the end */
+  uint32_t* d_taken = small_buf.p + n_grid;
+  VM_HIP_TRY(hipMemsetAsync(d_taken, 0, (size_t)n_grid * 4, st), "zero taken");
   size_t total = (size_t)n * n_grid;
   uint32_t eblocks = (uint32_t)std::min<size_t>((total + 255) / 256, 4096);
-  hipLaunchKernelGGL(topk_col_hist_kernel, dim3(eblocks), dim3(256), 0, st,
-                     b.d_out, n, n_grid, reverse, d_hists);
-  hipLaunchKernelGGL(topk_col_threshold_kernel,
-                     dim3((n_grid + 255) / 256), dim3(256), 0, st,
-                     d_hists, n_grid, kk, d_bins, d_bins + n_grid);
-  hipLaunchKernelGGL(topk_col_candidates_kernel, dim3(eblocks), dim3(256), 0, st,
-                     b.d_out, n, n_grid, reverse, d_bins, d_cand, d_cand_n,
-                     CAND_CAP, d_overflow);
-  uint32_t overflow_h = 0;
-  VM_HIP_TRY(hipMemcpyAsync(&overflow_h, d_overflow, 4, hipMemcpyDeviceToHost, st), "dl ovf");
-  VM_HIP_TRY(hipStreamSynchronize(st), "sync ovf");
-  if (overflow_h)
-    return vm_set_err(errbuf, errbuf_len,
-                      "vmgpu: topk candidate overflow (massive ties); unsupported");
-  hipLaunchKernelGGL(topk_col_kstar_kernel, dim3(n_grid), dim3(256), 0, st,
-                     d_cand, d_cand_n, CAND_CAP, d_bins + n_grid, kk, n_grid,
-                     d_kstar, d_ties);
+  for (int shift = 48; shift >= 0; shift -= 16) {
+    VM_HIP_TRY(hipMemsetAsync(d_hists, 0, (size_t)n_grid * 65536 * 4, st), "zero hists");
+    hipLaunchKernelGGL(topk_col_hist_kernel, dim3(eblocks), dim3(256), 0, st,
+                       b.d_out, n, n_grid, reverse, d_kstar, shift, d_hists);
+    hipLaunchKernelGGL(topk_col_refine_kernel, dim3(n_grid),
+                       dim3(BLOCK_THREADS), 0, st, d_hists, n_grid, kk,
+                       shift == 48 ? 1 : 0, d_kstar, d_need);
+  }
   hipLaunchKernelGGL(topk_col_fill_kernel, dim3(eblocks), dim3(256), 0, st,
-                     b.d_out, n, n_grid, reverse, kk, d_bins, d_kstar, d_taken,
-                     d_ties);
+                     b.d_out, n, n_grid, reverse, d_kstar, d_need, d_taken);
   if (out) {
     VM_HIP_TRY(hipMemcpyAsync(out, b.d_out, total * 8, hipMemcpyDeviceToHost, st), "dl out");
   }

@@ -626,6 +626,7 @@ class SeriesBatch:
                     last_kernel_ms(), scanned.value)
         self._last_rows = self.n_groups if grouped else self.n_series
         self._last_n_grid = n_grid
+        self._last_grouped = grouped
         if out is not None and not grouped and \
                 getattr(self, "_perm", None) is not None:
             # physical row i holds original series _perm[i]
@@ -793,9 +794,20 @@ def aggr_finalize(aggr, values, counts):
 TOPK_SUMMARY_OPS = {"avg": 0, "min": 1, "max": 2, "median": 3, "last": 4}
 
 
+def _series_perm(batch):
+    """Physical-row -> original-series map of the batch's last output, or
+    None when its rows are already in the caller's order (no relayout, or
+    a grouped output, whose rows are group ids)."""
+    if getattr(batch, "_last_grouped", False):
+        return None
+    return getattr(batch, "_perm", None)
+
+
 def topk_range(batch, k, summary="avg", reverse=False, remaining=False):
     """getRangeTopKTimeseries over the batch's last evaluated output:
-    returns (selected row ids in output order, remaining-sum row or None)."""
+    returns (selected row ids in output order, remaining-sum row or None).
+    The ids are ORIGINAL series ids, also on a group-relayouted batch; rows
+    with equal summaries come in descending physical row order there."""
     lib = _load_lib()
     rows = batch._last_rows or batch.n_series
     # topk(inf, q) selects everything (lessWithNaNs tolerates any float k);
@@ -822,12 +834,18 @@ def topk_range(batch, k, summary="avg", reverse=False, remaining=False):
         ctypes.byref(n_sel), rptr, errbuf, ctypes.c_size_t(256))
     if rc != 0:
         raise VmGpuError(f"vmgpu_topk_range failed ({rc}): {errbuf.value.decode()}")
-    return sel[:n_sel.value], rem
+    sel = sel[:n_sel.value]
+    perm = _series_perm(batch)
+    if perm is not None:
+        # physical row i holds original series perm[i]
+        sel = perm[sel].astype(np.int64)
+    return sel, rem
 
 
 def topk_pointwise(batch, k, reverse=False):
     """newAggrFuncTopK over the batch's last evaluated output: returns the
-    [rows x n_grid] matrix with all but the per-point top k NaN-filled.
+    [rows x n_grid] matrix with all but the per-point top k NaN-filled, rows
+    in ORIGINAL series order also on a group-relayouted batch.
     NOTE: mutates the device-resident output."""
     lib = _load_lib()
     rows = batch._last_rows
@@ -841,6 +859,11 @@ def topk_pointwise(batch, k, reverse=False):
         errbuf, ctypes.c_size_t(256))
     if rc != 0:
         raise VmGpuError(f"vmgpu_topk_pointwise failed ({rc}): {errbuf.value.decode()}")
+    perm = _series_perm(batch)
+    if perm is not None:
+        orig = np.empty_like(out)
+        orig[perm] = out
+        out = orig
     return out
 
 
