@@ -490,6 +490,48 @@ int vmgpu_count_values_over_time_fetch(uint64_t handle, uint32_t* row_series,
                                        double* row_value, double* out,
                                        char* errbuf, size_t errbuf_len);
 
+/* histogram() aggregate (aggrFuncHistogram, aggr.go:316) over the rows of a
+ * [n_series x n_grid] matrix, grouped by a member CSR: group g owns the rows
+ * group_rows[group_offsets[g] .. group_offsets[g + 1]), in any order,
+ * contiguous or not.  Per (group, grid point) the member values are
+ * classified with the table of vmgpu_vmrange_thresholds_set (which must have
+ * been set); NaN and v < 0 (-Inf included) contribute nothing, -0.0 counts
+ * as 0.  The output is SPARSE like the histogram rollup's: one row per
+ * (group, vmrange code) that is non-zero at one or more grid points, ordered
+ * by group and then by ascending code.
+ *
+ * vmgpu_aggr_histogram_exec: values is a HOST matrix, uploaded for the call.
+ * vmgpu_batch_aggr_histogram_exec: the matrix is the resident output of the
+ *   batch's last vmgpu_rollup_exec, which never leaves the device and is
+ *   only read; group_rows are PHYSICAL output rows (vmgpu_batch_perm maps
+ *   them to original series ids on a relayouted batch).  A batch without a
+ *   last output is an error.
+ *   Both run the mark pass, the row scan and the count pass, return the row
+ *   count, report their kernel time through vmgpu_last_kernel_ms and leave
+ *   the result resident in the library context, replacing the earlier one
+ *   (vmgpu_shutdown frees it).  Errors, all before any kernel is launched:
+ *   group_offsets not non-decreasing from 0 or with more than 2^32 - 1
+ *   members, a group_rows entry >= the row count, n_grid <= 0 or above 2^30,
+ *   a result whose n_rows x n_grid x 8 bytes could exceed 63 bits.  Zero
+ *   groups or zero members give 0 rows and launch nothing.  A failed call
+ *   leaves no result.
+ * vmgpu_aggr_histogram_fetch: downloads the last result of either exec:
+ *   row_group[n_rows], row_code[n_rows] (0 = lower, 1..486 = bucket idx
+ *   0..485, 487 = upper) and out[n_rows x n_grid], the count as f64 — 0.0,
+ *   NOT NaN, where it is zero: the reference starts its rows from zeros.
+ *   Any destination may be NULL.  Without a valid result it is an error. */
+int vmgpu_aggr_histogram_exec(const double* values, uint32_t n_series,
+                              int32_t n_grid, const uint32_t* group_rows,
+                              const uint64_t* group_offsets, uint32_t n_groups,
+                              uint64_t* out_n_rows,
+                              char* errbuf, size_t errbuf_len);
+int vmgpu_batch_aggr_histogram_exec(uint64_t handle, const uint32_t* group_rows,
+                                    const uint64_t* group_offsets,
+                                    uint32_t n_groups, uint64_t* out_n_rows,
+                                    char* errbuf, size_t errbuf_len);
+int vmgpu_aggr_histogram_fetch(uint32_t* row_group, uint16_t* row_code,
+                               double* out, char* errbuf, size_t errbuf_len);
+
 /* Pinned host buffers for PCIe-rate staging of payloads and results (the
  * cgo layer would pool these; hipHostMalloc/-Free underneath). */
 int vmgpu_host_alloc(uint64_t nbytes, void** out_ptr);

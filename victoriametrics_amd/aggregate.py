@@ -13,7 +13,15 @@ on the GPU:
   newAggrFuncRangeTopK / aggrFuncOutliersK, aggr.go:669-802); the
   batch-resident selection path stays on the device kernels
   (engine.topk_range / topk_pointwise);
-- any / limitk are metadata selections (host).
+- any / limitk are metadata selections (host);
+- histogram: histogram_aggregate is the host reference (a Python loop over
+  groups x grid points x members); histogram_aggregate_device runs that
+  loop through engine.aggr_histogram (csrc/aggrhist.hip: sparse mark / row
+  scan / count over a member CSR) and histogram_aggregate_batch does the
+  same over a SeriesBatch's resident rollup output, which then never
+  crosses PCIe.  Naming and vmrangeBucketsToLE stay on the host (at most
+  488 rows a group).  aggregate("histogram") is not routed there yet, and
+  count_values is still host-only.
 
 This layer exists for aggregation over RESIDENT result series (e.g. after
 binary ops or transforms).  The rollup->aggregate hot path keeps using the
@@ -545,6 +553,67 @@ def histogram_aggregate(series, modifier_op="", modifier_args=(), limit=0):
                 ts.values[i] = float(count)
         rvs.extend(m.values())
     return vmrange_buckets_to_le(rvs)
+
+
+def _histogram_rows_to_le(group_mns, row_group, row_code, values):
+    """One Series per sparse device row, named as histogram_aggregate names
+    it (the group name, any existing vmrange tag replaced), then
+    vmrangeBucketsToLE.  Rows come ordered by (group, ascending bucket)."""
+    from .rollup_multi import vmrange_label  # imports this module
+    from .transform import vmrange_buckets_to_le
+    rvs = []
+    for i in range(len(row_group)):
+        mn = group_mns[int(row_group[i])].copy()
+        mn.remove_tag("vmrange")
+        mn.add_tag("vmrange", vmrange_label(int(row_code[i])))
+        rvs.append(Series(mn, values[i]))
+    return vmrange_buckets_to_le(rvs)
+
+
+def histogram_aggregate_device(series, modifier_op="", modifier_args=(),
+                               limit=0):
+    """histogram_aggregate with the groups x grid points x members loop on
+    the device (engine.aggr_histogram, csrc/aggrhist.hip): same arguments,
+    same result.  The device classifies with the threshold table built from
+    _histogram_update itself, so every count is the host function's."""
+    groups = prepare_series(series, modifier_op, modifier_args, limit)
+    if not groups:
+        return []
+    v, gr, go = _matrix(groups)
+    row_group, row_code, values = engine.aggr_histogram(v, gr, go)
+    return _histogram_rows_to_le([gmn for gmn, _ in groups], row_group,
+                                 row_code, values)
+
+
+def histogram_aggregate_batch(batch, metric_names, modifier_op="",
+                              modifier_args=(), limit=0):
+    """histogram_aggregate over the resident output of a SeriesBatch's last
+    ungrouped exec: the rolled-up matrix stays on the device
+    (SeriesBatch.aggr_histogram).  metric_names[s] names ORIGINAL series s
+    as the rollup left it; the grouping comes from those names.
+
+    A series whose output row is all NaN stays in its group: it classifies
+    to nothing and creates no row, so the result is that of the host
+    function, which drops such series first (remove_empty_series).  The one
+    visible difference: with limit > 0 a group whose members are ALL empty
+    still takes one of the limit's slots here."""
+    m = {}
+    group_mns = []
+    group_of = np.full(len(metric_names), -1, dtype=np.int32)
+    for s, name in enumerate(metric_names):
+        mn = name.copy()
+        remove_group_tags(mn, modifier_op, modifier_args)
+        k = mn.marshal_sorted()
+        g = m.get(k)
+        if g is None:
+            if limit > 0 and len(m) >= limit:
+                continue
+            g = m[k] = len(group_mns)
+            group_mns.append(mn)
+        group_of[s] = g
+    row_group, row_code, values = batch.aggr_histogram(group_of,
+                                                       len(group_mns))
+    return _histogram_rows_to_le(group_mns, row_group, row_code, values)
 
 
 def quantiles(dst_label, phis, series, modifier_op="", modifier_args=(),

@@ -285,6 +285,8 @@ void vm_hot_state_free(vm_hot_state* h) {
   *h = vm_hot_state();
 }
 
+const double* vm_hot_thresholds(void) { return g_d_thr; }
+
 void vm_hot_shutdown(void) {
   (void)vm_dev_free(g_d_thr);
   g_d_thr = nullptr;

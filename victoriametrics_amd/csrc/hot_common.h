@@ -69,6 +69,11 @@ static HOT_DEV bool hot_grid_range(const HotParams& p, int64_t ts,
 void hot_scan_launch(const uint32_t* row_counts, uint32_t n,
                      uint64_t* row_start, hipStream_t st);
 
+/* hot.hip: the device copy of the table vmgpu_vmrange_thresholds_set
+ * uploaded (VMRANGE_TABLE_PAD doubles, NaN-padded), NULL before the first
+ * upload.  The caller holds the context lock. */
+const double* vm_hot_thresholds(void);
+
 /* Grow-only reservation with plain hipMalloc.  Deliberately NOT the
  * stream-ordered pool of devalloc.h: the result size changes from call to
  * call, and a free-then-larger-malloc cycle through the pool right before

@@ -2834,6 +2834,7 @@ int vmgpu_shutdown(void) {
   for (auto& kv : g_ctx.batches) free_batch(kv.second);
   g_ctx.batches.clear();
   vm_hot_shutdown();
+  vm_aggrhist_shutdown();
   (void)hipEventDestroy(g_ctx.ev_start);
   (void)hipEventDestroy(g_ctx.ev_stop);
   (void)hipStreamDestroy(g_ctx.stream);

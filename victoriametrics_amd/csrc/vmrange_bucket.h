@@ -33,14 +33,20 @@
 #endif
 
 /* thr: VMRANGE_TABLE_PAD doubles (LDS on the device).  Branchless 9-step
- * lower-bound search. */
-VMRANGE_FN uint32_t vmrange_bucket_code(const double* thr, double v) {
-  if (v != v || v < 0) return VMRANGE_CODE_NONE; /* -0.0 is not < 0 */
+ * lower-bound search; the code of v when v is neither NaN nor negative (0
+ * for those, to be discarded by the caller).  On its own for callers that
+ * run several searches side by side. */
+VMRANGE_FN uint32_t vmrange_bucket_search(const double* thr, double v) {
   uint32_t pos = 0;
 #pragma unroll
   for (uint32_t step = VMRANGE_TABLE_PAD / 2; step; step >>= 1)
     pos += (thr[pos + step - 1] <= v) ? step : 0;
   return pos;
+}
+
+VMRANGE_FN uint32_t vmrange_bucket_code(const double* thr, double v) {
+  if (v != v || v < 0) return VMRANGE_CODE_NONE; /* -0.0 is not < 0 */
+  return vmrange_bucket_search(thr, v);
 }
 
 #endif /* VMGPU_VMRANGE_BUCKET_H */

@@ -720,6 +720,52 @@ class SeriesBatch:
                              f"({rc}): {errbuf.value.decode()}")
         return row_series, row_value, values, scanned.value
 
+    def aggr_histogram(self, group_of, n_groups):
+        """histogram() aggregate over the resident output of the last
+        ungrouped exec, on the device (csrc/aggrhist.hip); the rolled-up
+        matrix never leaves the device and is only read.  group_of[s] is
+        the group of ORIGINAL series s (int32, -1 = in no group); the
+        physical member CSR is built here through the batch's permutation.
+        Returns (row_group u32[n_rows], row_code u16[n_rows], values
+        f64[n_rows, n_grid]) as engine.aggr_histogram does.  Raises
+        VmGpuError after a grouped exec: those output rows are groups, not
+        series."""
+        _check_array("group_of", group_of, np.int32, 1)
+        n_groups = int(n_groups)
+        if len(group_of) != self.n_series:
+            raise ValueError(f"group_of has {len(group_of)} entries for "
+                             f"{self.n_series} series")
+        if n_groups < 0 or (len(group_of) and (
+                group_of.min() < -1 or group_of.max() >= n_groups)):
+            raise ValueError("group_of entries must lie in [-1, n_groups)")
+        if getattr(self, "_last_grouped", False):
+            raise VmGpuError(
+                "aggr_histogram needs the output of an ungrouped exec; the "
+                "rows of the last exec are groups, not series")
+        perm = getattr(self, "_perm", None)
+        g_phys = group_of[perm] if perm is not None else group_of
+        rows = np.flatnonzero(g_phys >= 0)
+        order = np.argsort(g_phys[rows], kind="stable")
+        group_rows = np.ascontiguousarray(rows[order], dtype=np.uint32)
+        group_offsets = np.zeros(n_groups + 1, dtype=np.uint64)
+        np.cumsum(np.bincount(g_phys[rows], minlength=n_groups),
+                  out=group_offsets[1:])
+        lib = _load_lib()
+        _upload_vmrange_thresholds(lib)
+        n_rows = ctypes.c_uint64(0)
+        errbuf = ctypes.create_string_buffer(256)
+        rc = lib.vmgpu_batch_aggr_histogram_exec(
+            ctypes.c_uint64(self.handle),
+            group_rows.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)),
+            group_offsets.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64)),
+            ctypes.c_uint32(n_groups), ctypes.byref(n_rows), errbuf,
+            ctypes.c_size_t(len(errbuf)))
+        if rc != 0:
+            raise VmGpuError(f"vmgpu_batch_aggr_histogram_exec failed ({rc}): "
+                             f"{errbuf.value.decode()}")
+        return _aggr_histogram_fetch(lib, n_rows.value,
+                                     getattr(self, "_last_n_grid", 0))
+
     def fetch_out_into(self, dst, n_grid):
         """Download the last exec's output rows directly into a caller
         buffer (e.g. a marshal buffer's values section) — no intermediate
@@ -1331,6 +1377,74 @@ def colagg_filter(mode, values, group_of, b1, b2):
         raise VmGpuError(f"vmgpu_colagg_filter failed ({rc}): "
                          f"{errbuf.value.decode()}")
     return flags
+
+
+def _check_array(name, a, dtype, ndim):
+    """The native calls take raw pointers: insist on the exact layout
+    instead of converting silently."""
+    if not isinstance(a, np.ndarray) or a.dtype != dtype:
+        raise TypeError(f"{name} must be a numpy array of {np.dtype(dtype)}")
+    if a.ndim != ndim:
+        raise ValueError(f"{name} must have {ndim} dimension(s); "
+                         f"got {a.ndim}")
+    if not a.flags.c_contiguous:
+        raise ValueError(f"{name} must be C-contiguous")
+
+
+def _aggr_histogram_fetch(lib, n_rows, n_grid):
+    row_group = np.empty(n_rows, dtype=np.uint32)
+    row_code = np.empty(n_rows, dtype=np.uint16)
+    values = np.empty((n_rows, n_grid), dtype=np.float64)
+    errbuf = ctypes.create_string_buffer(256)
+    rc = lib.vmgpu_aggr_histogram_fetch(
+        row_group.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)),
+        row_code.ctypes.data_as(ctypes.POINTER(ctypes.c_uint16)),
+        values.ctypes.data_as(ctypes.POINTER(ctypes.c_double)),
+        errbuf, ctypes.c_size_t(len(errbuf)))
+    if rc != 0:
+        raise VmGpuError(f"vmgpu_aggr_histogram_fetch failed ({rc}): "
+                         f"{errbuf.value.decode()}")
+    return row_group, row_code, values
+
+
+def aggr_histogram(values, group_rows, group_offsets):
+    """histogram() aggregate (aggrFuncHistogram) over member rows per group,
+    on the device (csrc/aggrhist.hip: mark pass, row scan, count pass).
+    values f64[n_series, n_grid]; group g owns the rows
+    group_rows[group_offsets[g]:group_offsets[g + 1]] (u32 / u64), in any
+    order.  The output is sparse: one row per (group, vmrange bucket) that
+    is non-zero at one or more grid points, ordered by group and then by
+    ascending bucket code (0 = lower, 1..486 = bucket idx 0..485,
+    487 = upper).  Returns (row_group u32[n_rows], row_code u16[n_rows],
+    values f64[n_rows, n_grid]); a zero count is 0.0, not NaN.  NaN and
+    negative values count nowhere.  The arrays must already have these
+    dtypes and be C-contiguous."""
+    _check_array("values", values, np.float64, 2)
+    _check_array("group_rows", group_rows, np.uint32, 1)
+    _check_array("group_offsets", group_offsets, np.uint64, 1)
+    if len(group_offsets) < 1:
+        raise ValueError("group_offsets needs n_groups + 1 entries")
+    n_series, n_grid = values.shape
+    n_groups = len(group_offsets) - 1
+    if n_series >= 2 ** 32 or n_grid >= 2 ** 31 or n_groups >= 2 ** 32:
+        raise ValueError("matrix or group count beyond the C ABI's range")
+    if n_groups and int(group_offsets[-1]) > len(group_rows):
+        raise ValueError("group_offsets runs past the end of group_rows")
+    lib = _load_lib()
+    _upload_vmrange_thresholds(lib)
+    n_rows = ctypes.c_uint64(0)
+    errbuf = ctypes.create_string_buffer(256)
+    rc = lib.vmgpu_aggr_histogram_exec(
+        values.ctypes.data_as(ctypes.POINTER(ctypes.c_double)),
+        ctypes.c_uint32(n_series), ctypes.c_int32(n_grid),
+        group_rows.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)),
+        group_offsets.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64)),
+        ctypes.c_uint32(n_groups), ctypes.byref(n_rows), errbuf,
+        ctypes.c_size_t(len(errbuf)))
+    if rc != 0:
+        raise VmGpuError(f"vmgpu_aggr_histogram_exec failed ({rc}): "
+                         f"{errbuf.value.decode()}")
+    return _aggr_histogram_fetch(lib, n_rows.value, n_grid)
 
 
 def quantiles_over_time_plans(phi_label, phis, start, end, step, **kwargs):
