@@ -532,6 +532,55 @@ int vmgpu_batch_aggr_histogram_exec(uint64_t handle, const uint32_t* group_rows,
 int vmgpu_aggr_histogram_fetch(uint32_t* row_group, uint16_t* row_code,
                                double* out, char* errbuf, size_t errbuf_len);
 
+/* count_values() aggregate (aggrFuncCountValues, aggr.go:566) over the rows
+ * of a [n_series x n_grid] matrix, grouped by the member CSR of the
+ * histogram() aggregate above.  The output is SPARSE: per group one row per
+ * distinct non-NaN value occurring anywhere in the group's members (every
+ * NaN is skipped, the stale NaN included; -0.0 and 0.0 are ONE row), ordered
+ * by group and then by ascending value, -Inf ... 0 ... +Inf.
+ *
+ * vmgpu_aggr_count_values_exec: values is a HOST matrix, uploaded for the
+ *   call.
+ * vmgpu_batch_aggr_count_values_exec: the matrix is the resident output of
+ *   the batch's last ungrouped vmgpu_rollup_exec, only read; group_rows are
+ *   PHYSICAL output rows.  A batch without a last output is an error.
+ *   max_rows_per_group, in [1, 2^24], bounds the distinct values of ONE
+ *   group and sizes the per-group tables (the power of two >= 2 x
+ *   min(limit + 1, members x n_grid) slots of 8 bytes, at least 64).  A
+ *   group with exactly that many distinct values succeeds; with more, the
+ *   call returns 1, names the smallest such group in errbuf and leaves no
+ *   result.  Both forms return the row count, report their kernel time
+ *   through vmgpu_last_kernel_ms and leave the result resident in the
+ *   library context, replacing the earlier one (vmgpu_shutdown frees it).
+ *   Errors before any kernel is launched: a limit outside [1, 2^24], the
+ *   CSR and grid errors of vmgpu_aggr_histogram_exec, a result bound
+ *   (sum over groups of min(limit, members x n_grid)) x n_grid x 8 bytes
+ *   beyond 63 bits, tables of more than 2^31 slots in all.  Zero groups or
+ *   zero members give 0 rows and launch nothing.  Any failed call leaves no
+ *   result.  The same input gives the same bits on every run.
+ * vmgpu_aggr_count_values_fetch: downloads the last result of either exec:
+ *   row_group[n_rows], row_value[n_rows] (the counted value; the zero row
+ *   carries the sign of the group's first zero in member order, then grid
+ *   order, which is the zero the reference names the series after) and
+ *   out[n_rows x n_grid], the number of members equal to the row's value
+ *   as f64 — NaN, NOT 0.0, where it is zero.  Any destination may be NULL.
+ *   Without a valid result it is an error. */
+int vmgpu_aggr_count_values_exec(const double* values, uint32_t n_series,
+                                 int32_t n_grid, const uint32_t* group_rows,
+                                 const uint64_t* group_offsets,
+                                 uint32_t n_groups, uint32_t max_rows_per_group,
+                                 uint64_t* out_n_rows,
+                                 char* errbuf, size_t errbuf_len);
+int vmgpu_batch_aggr_count_values_exec(uint64_t handle,
+                                       const uint32_t* group_rows,
+                                       const uint64_t* group_offsets,
+                                       uint32_t n_groups,
+                                       uint32_t max_rows_per_group,
+                                       uint64_t* out_n_rows,
+                                       char* errbuf, size_t errbuf_len);
+int vmgpu_aggr_count_values_fetch(uint32_t* row_group, double* row_value,
+                                  double* out, char* errbuf, size_t errbuf_len);
+
 /* Pinned host buffers for PCIe-rate staging of payloads and results (the
  * cgo layer would pool these; hipHostMalloc/-Free underneath). */
 int vmgpu_host_alloc(uint64_t nbytes, void** out_ptr);

@@ -20,8 +20,14 @@ on the GPU:
   scan / count over a member CSR) and histogram_aggregate_batch does the
   same over a SeriesBatch's resident rollup output, which then never
   crosses PCIe.  Naming and vmrangeBucketsToLE stay on the host (at most
-  488 rows a group).  aggregate("histogram") is not routed there yet, and
-  count_values is still host-only.
+  488 rows a group).  aggregate("histogram") is not routed there yet;
+- count_values: count_values is the host reference (a Python loop over
+  groups x members x grid points with a dict lookup per value);
+  count_values_device runs it through engine.aggr_count_values
+  (csrc/aggrcv.hip: per-group hash insert / row scan / sort / count over
+  the same member CSR) and count_values_batch over a SeriesBatch's resident
+  rollup output.  One row per distinct value of a group, at most
+  max_series_per_aggr of them; naming stays on the host.
 
 This layer exists for aggregation over RESIDENT result series (e.g. after
 binary ops or transforms).  The rollup->aggregate hot path keeps using the
@@ -470,6 +476,95 @@ def count_values(dst_label, series, modifier_op="", modifier_args=(),
                     dst.values[i] += 1.0
         rvs.extend(m[k] for k in order)
     return rvs
+
+
+def _count_values_group_args(dst_label, modifier_op, modifier_args):
+    """dst_label leaves the grouping, as count_values does it."""
+    modifier_args = list(modifier_args)
+    op = (modifier_op or "").lower()
+    if op == "without":
+        modifier_args = modifier_args + [dst_label]
+    elif op == "by":
+        modifier_args = [a for a in modifier_args if a != dst_label]
+    return modifier_args
+
+
+def _count_values_rows_to_series(dst_label, group_mns, row_group, row_value,
+                                 values):
+    """One Series per sparse device row, named as count_values names it: the
+    group name with dst_label replaced by the formatted value.  Rows come
+    ordered by (group, ascending value)."""
+    rvs = []
+    for i in range(len(row_group)):
+        mn = group_mns[int(row_group[i])].copy()
+        mn.remove_tag(dst_label)
+        mn.add_tag(dst_label, format_go_float(float(row_value[i])))
+        rvs.append(Series(mn, values[i]))
+    return rvs
+
+
+def _count_values_limit_error(max_series_per_aggr):
+    return ValueError(f"more than {max_series_per_aggr} series generated by "
+                      "count_values()")
+
+
+def count_values_device(dst_label, series, modifier_op="", modifier_args=(),
+                        limit=0, max_series_per_aggr=1000):
+    """count_values with the groups x members x grid points loop on the
+    device (engine.aggr_count_values, csrc/aggrcv.hip): same arguments and
+    the same series, ordered per group by ascending value instead of by
+    first sight.  max_series_per_aggr bounds the distinct values of one
+    group, as len(m) does in the host function."""
+    modifier_args = _count_values_group_args(dst_label, modifier_op,
+                                             modifier_args)
+    groups = prepare_series(series, modifier_op, modifier_args, limit)
+    if not groups:
+        return []
+    v, gr, go = _matrix(groups)
+    try:
+        row_group, row_value, values = engine.aggr_count_values(
+            v, gr, go, max_series_per_aggr)
+    except engine.CountValuesLimitError:
+        raise _count_values_limit_error(max_series_per_aggr) from None
+    return _count_values_rows_to_series(dst_label, [gmn for gmn, _ in groups],
+                                        row_group, row_value, values)
+
+
+def count_values_batch(dst_label, batch, metric_names, modifier_op="",
+                       modifier_args=(), limit=0, max_series_per_aggr=1000):
+    """count_values over the resident output of a SeriesBatch's last
+    ungrouped exec: the rolled-up matrix stays on the device
+    (SeriesBatch.aggr_count_values).  metric_names[s] names ORIGINAL series
+    s as the rollup left it; the grouping comes from those names.
+
+    A series whose output row is all NaN stays in its group: it holds no
+    value and creates no row, so the result is that of the host function,
+    which drops such series first (remove_empty_series).  The one visible
+    difference: with limit > 0 a group whose members are ALL empty still
+    takes one of the limit's slots here."""
+    modifier_args = _count_values_group_args(dst_label, modifier_op,
+                                             modifier_args)
+    m = {}
+    group_mns = []
+    group_of = np.full(len(metric_names), -1, dtype=np.int32)
+    for s, name in enumerate(metric_names):
+        mn = name.copy()
+        remove_group_tags(mn, modifier_op, modifier_args)
+        k = mn.marshal_sorted()
+        g = m.get(k)
+        if g is None:
+            if limit > 0 and len(m) >= limit:
+                continue
+            g = m[k] = len(group_mns)
+            group_mns.append(mn)
+        group_of[s] = g
+    try:
+        row_group, row_value, values = batch.aggr_count_values(
+            group_of, len(group_mns), max_series_per_aggr)
+    except engine.CountValuesLimitError:
+        raise _count_values_limit_error(max_series_per_aggr) from None
+    return _count_values_rows_to_series(dst_label, group_mns, row_group,
+                                        row_value, values)
 
 
 # ---------------------------------------------------------------------------

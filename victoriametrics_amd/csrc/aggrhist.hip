@@ -33,9 +33,9 @@
  *       more rows than the tile holds is counted in bands of AH_BAND_ROWS.
  *   ah_u32_to_f64_kernel counters -> f64 result.
  *
- * The chunk list, the row scan and the counter conversion know nothing
- * about vmrange codes; a count_values() aggregate can reuse them with its
- * own row discovery.
+ * The chunk list, the CSR checks and the counter conversion know nothing
+ * about vmrange codes: they live in aggr_sparse.h, and the count_values()
+ * aggregate (aggrcv.hip) uses them with its own row discovery.
  *
  * Result and scratch live in one file-static slot (the aggregate has no
  * batch of its own to hang them on), grow-only, plain hipMalloc through
@@ -49,6 +49,7 @@
 #include <mutex>
 #include <vector>
 
+#include "aggr_sparse.h"
 #include "batch_access.h"
 #include "hot_common.h"
 #include "vmrange_bucket.h"
@@ -70,12 +71,6 @@
 #define AH_COUNT_THREADS 128
 #define AH_MARK_WAVES (AH_MARK_THREADS / HOT_WAVE)
 #define AH_COUNT_WAVES (AH_COUNT_THREADS / HOT_WAVE)
-
-struct AhChunk {
-  uint64_t begin; /* first member, index into group_rows */
-  uint32_t n;     /* 1..AH_CHUNK_MEMBERS */
-  uint32_t group;
-};
 
 /* cache the code of one value and note it in the wave's mask */
 static HOT_DEV void ah_mark_put(uint32_t* s_mask, uint32_t code,
@@ -267,13 +262,6 @@ __global__ __launch_bounds__(AH_COUNT_THREADS) void ah_count_kernel(
   }
 }
 
-__global__ __launch_bounds__(256) void ah_u32_to_f64_kernel(
-    const uint32_t* __restrict__ cnt, uint64_t n, double* __restrict__ out) {
-  for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n;
-       i += (uint64_t)gridDim.x * blockDim.x)
-    out[i] = (double)cnt[i];
-}
-
 /* ------------------------------------------------------------------ */
 /* host side                                                          */
 /* ------------------------------------------------------------------ */
@@ -307,57 +295,19 @@ struct AhState {
 
 AhState g_ah;
 
-/* every group cut into chunks of at most AH_CHUNK_MEMBERS members */
-void ah_build_chunks(const uint64_t* group_offsets, uint32_t n_groups,
-                     std::vector<AhChunk>* chunks) {
-  chunks->clear();
-  for (uint32_t g = 0; g < n_groups; g++)
-    for (uint64_t lo = group_offsets[g]; lo < group_offsets[g + 1];
-         lo += AH_CHUNK_MEMBERS) {
-      AhChunk c;
-      c.begin = lo;
-      c.n = (uint32_t)std::min<uint64_t>(AH_CHUNK_MEMBERS, group_offsets[g + 1] - lo);
-      c.group = g;
-      chunks->push_back(c);
-    }
-}
-
-uint32_t ah_blocks(uint64_t work, uint32_t per_block) {
-  return (uint32_t)std::min<uint64_t>((work + per_block - 1) / per_block,
-                                      HOT_MAX_BLOCKS);
-}
-
 /* Argument checks shared by both entry points; nothing is launched or
  * allocated before they pass.  Returns 0 or the vm_set_err code. */
 int ah_validate(uint32_t n_in_rows, int64_t n_grid, const uint32_t* group_rows,
                 const uint64_t* group_offsets, uint32_t n_groups,
                 char* errbuf, size_t errbuf_len) {
-  if (n_grid <= 0 || n_grid > (int64_t)1 << 30)
-    return vm_set_err(errbuf, errbuf_len, "vmgpu: aggr histogram: bad grid");
+  if (int rc = ah_validate_csr("aggr histogram", n_in_rows, n_grid, group_rows,
+                               group_offsets, n_groups, errbuf, errbuf_len))
+    return rc;
   if (n_groups == 0) return 0;
-  if (!group_offsets)
-    return vm_set_err(errbuf, errbuf_len, "vmgpu: aggr histogram: bad args");
-  if (group_offsets[0] != 0)
-    return vm_set_err(errbuf, errbuf_len,
-                      "vmgpu: aggr histogram: group_offsets must start at 0");
-  for (uint32_t g = 0; g < n_groups; g++)
-    if (group_offsets[g + 1] < group_offsets[g])
-      return vm_set_err(errbuf, errbuf_len,
-                        "vmgpu: aggr histogram: group_offsets must not decrease");
-  const uint64_t n_members = group_offsets[n_groups];
-  if (n_members > 0xFFFFFFFFull)
-    return vm_set_err(errbuf, errbuf_len,
-                      "vmgpu: aggr histogram: more than 2^32 - 1 members");
-  if (n_members && !group_rows)
-    return vm_set_err(errbuf, errbuf_len, "vmgpu: aggr histogram: bad args");
-  for (uint64_t k = 0; k < n_members; k++)
-    if (group_rows[k] >= n_in_rows)
-      return vm_set_err(errbuf, errbuf_len,
-                        "vmgpu: aggr histogram: group_rows entry out of range");
   /* a group with members has at most 488 rows: bound the result before any
    * kernel runs */
   const uint64_t max_rows =
-      std::min<uint64_t>(n_groups, n_members) * VMRANGE_N_CODES;
+      std::min<uint64_t>(n_groups, group_offsets[n_groups]) * VMRANGE_N_CODES;
   if (max_rows > (uint64_t)INT64_MAX / 8 / (uint64_t)n_grid)
     return vm_set_err(errbuf, errbuf_len,
                       "vmgpu: aggr histogram: result size overflows");
@@ -386,7 +336,7 @@ int ah_run(const double* d_vals, uint32_t n_in_rows, int32_t n_grid,
                       "vmgpu: vmrange threshold table not uploaded "
                       "(vmgpu_vmrange_thresholds_set)");
   std::vector<AhChunk> chunks;
-  ah_build_chunks(group_offsets, n_groups, &chunks);
+  ah_build_chunks(group_offsets, n_groups, AH_CHUNK_MEMBERS, &chunks);
   const uint32_t n_tiles = ((uint32_t)n_grid + AH_TILE_COLS - 1) / AH_TILE_COLS;
   const uint64_t n_items = (uint64_t)chunks.size() * n_tiles;
 
@@ -452,7 +402,7 @@ int ah_run(const double* d_vals, uint32_t n_in_rows, int32_t n_grid,
                        dim3(AH_COUNT_THREADS), 0, st, a.d_codes, (uint32_t)n_grid,
                        a.d_group_rows, a.d_chunks, n_items, n_tiles, a.d_masks,
                        a.d_row_start, a.d_cnt);
-    hipLaunchKernelGGL(ah_u32_to_f64_kernel, dim3(ah_blocks(n_out, 256)), dim3(256),
+    hipLaunchKernelGGL(ah_u32_to_f64_kernel<false>, dim3(ah_blocks(n_out, 256)), dim3(256),
                        0, st, a.d_cnt, n_out, a.d_out);
   }
   VM_HIP_TRY(hipEventRecord(ev_stop, st), "event stop");

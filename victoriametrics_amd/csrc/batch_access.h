@@ -1,6 +1,6 @@
 /* Narrow internal window onto a resident batch for entry points that live
- * outside vmgpu.hip (hot.hip, cvot.hip, topk.hip, aggrhist.hip; hstat.hip
- * takes only the context lock from here).  Batch itself stays private.  Same spirit as
+ * outside vmgpu.hip (hot.hip, cvot.hip, topk.hip, aggrhist.hip, aggrcv.hip;
+ * hstat.hip takes only the context lock from here).  Batch itself stays private.  Same spirit as
  * vm_ctx_stream (devalloc.h): the caller runs on the context stream and
  * holds the context lock for as long as it uses what it got here. */
 #ifndef VMGPU_BATCH_ACCESS_H
@@ -93,5 +93,8 @@ void vm_hot_shutdown(void);
 /* aggrhist.hip: free the histogram() aggregate's result and scratch (called
  * from vmgpu_shutdown with the context lock held) */
 void vm_aggrhist_shutdown(void);
+
+/* aggrcv.hip: the same for the count_values() aggregate */
+void vm_aggrcv_shutdown(void);
 
 #endif

@@ -30,15 +30,8 @@
  *       sum, f64 write with 0 -> NaN, as hot_count_kernel, but tiled over
  *       rows as well as over the grid; also row_series and row_value.
  *
- * The sort is the normalised bitonic network: every comparator orders its
- * pair ascending, so an index >= n can stand for +max without being stored
- * (such a comparator never moves anything) and n needs no padding.
- *
- * Order key of value bits u (all NaNs first folded to HOT_NAN_BITS):
- *   (u >> 63) ? ~u : u | 1 << 63
- * unsigned-ascending = -Inf ... -0 < 0 ... +Inf < NaN.  The largest real key
- * is NaN's 0xFFF8000000000000, so all-ones is free for CVOT_KEY_NONE, which
- * sorts behind every row.
+ * The order key, the bitonic sort and the search are value_key.h's, shared
+ * with the count_values() aggregate (aggrcv.hip).
  */
 #include <hip/hip_runtime.h>
 #include <algorithm>
@@ -48,14 +41,9 @@
 #include "batch_access.h"
 #include "devalloc.h"
 #include "hot_common.h"
+#include "value_key.h"
 #include "../../include/vmgpu.h"
 
-/* one wave sorts this many keys in a 2 KiB slab: 8 KiB a workgroup, so LDS
- * never limits the short class's occupancy; covers the 240-sample shape */
-#define CVOT_WAVE_CAP 256
-/* one workgroup sorts this many keys in 16 KiB of LDS: eight such
- * workgroups, the CU's 32 waves, still fit its 160 KiB */
-#define CVOT_BLOCK_CAP 2048
 /* workgroups of the long-series kernel: 8 per CU on 256 CUs; with an empty
  * list they read one word and leave */
 #define CVOT_LONG_BLOCKS 2048
@@ -65,18 +53,6 @@
  * row, so a tile row is still a ~500-byte contiguous output write */
 #define CVOT_ROW_TILE 24
 #define CVOT_ROW_NONE 0xFFFFFFFFu
-#define CVOT_KEY_NONE 0xFFFFFFFFFFFFFFFFULL
-
-static HOT_DEV uint64_t cvot_order_key(double v) {
-  uint64_t u = (uint64_t)__double_as_longlong(v);
-  if (v != v) u = HOT_NAN_BITS;
-  return (u >> 63) ? ~u : (u | (1ULL << 63));
-}
-
-static HOT_DEV double cvot_key_value(uint64_t k) {
-  const uint64_t u = (k >> 63) ? (k ^ (1ULL << 63)) : ~k;
-  return __longlong_as_double((long long)u);
-}
 
 /* order key of a covered sample (adding its grid-range length to sc), or
  * CVOT_KEY_NONE for a dropped stale NaN or a sample in no window */
@@ -89,62 +65,6 @@ static HOT_DEV uint64_t cvot_sample_key(const HotParams& p, int64_t t, double v,
   if (!hot_grid_range(p, t, g0, g1)) return CVOT_KEY_NONE;
   sc += (unsigned long long)(g1 - g0 + 1);
   return cvot_order_key(v);
-}
-
-template <bool WAVE>
-static HOT_DEV void cvot_sync() {
-  if (WAVE) hot_wave_sync();
-  else __syncthreads();
-}
-
-static HOT_DEV void cvot_cmpxchg(uint64_t* keys, uint64_t a, uint64_t b) {
-  const uint64_t x = keys[a], y = keys[b];
-  if (x > y) {
-    keys[a] = y;
-    keys[b] = x;
-  }
-}
-
-/* Ascending sort of keys[0..n) by nthr cooperating threads (one wave on its
- * slab, or one workgroup on LDS or global memory).  The caller has made
- * keys visible; the sort ends on a sync.  All trip counts are uniform. */
-template <bool WAVE>
-static HOT_DEV void cvot_sort(uint64_t* keys, uint64_t n, uint32_t tid,
-                              uint32_t nthr) {
-  if (n < 2) return;
-  uint64_t P = 2;
-  while (P < n) P <<= 1;
-  const uint64_t pairs = P >> 1;
-  for (uint64_t k = 2; k <= P; k <<= 1) {
-    const uint64_t half = k >> 1;
-    /* flip: pair x of a k-block meets its mirror image k-1-x */
-    for (uint64_t t = tid; t < pairs; t += nthr) {
-      const uint64_t a = ((t & ~(half - 1)) << 1) | (t & (half - 1));
-      const uint64_t b = a ^ (k - 1);
-      if (b < n) cvot_cmpxchg(keys, a, b);
-    }
-    cvot_sync<WAVE>();
-    for (uint64_t j = half >> 1; j; j >>= 1) {
-      for (uint64_t t = tid; t < pairs; t += nthr) {
-        const uint64_t a = ((t & ~(j - 1)) << 1) | (t & (j - 1));
-        const uint64_t b = a | j;
-        if (b < n) cvot_cmpxchg(keys, a, b);
-      }
-      cvot_sync<WAVE>();
-    }
-  }
-}
-
-/* first index in sorted keys[0..R) whose key is not below key */
-static HOT_DEV uint32_t cvot_lower_bound(const uint64_t* keys, uint32_t R,
-                                         uint64_t key) {
-  uint32_t lo = 0, hi = R;
-  while (lo < hi) {
-    const uint32_t mid = lo + (hi - lo) / 2;
-    if (keys[mid] < key) lo = mid + 1;
-    else hi = mid;
-  }
-  return lo;
 }
 
 __global__ __launch_bounds__(HOT_BLOCK_THREADS) void cvot_mark_kernel(

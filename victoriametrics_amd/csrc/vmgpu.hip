@@ -2835,6 +2835,7 @@ int vmgpu_shutdown(void) {
   g_ctx.batches.clear();
   vm_hot_shutdown();
   vm_aggrhist_shutdown();
+  vm_aggrcv_shutdown();
   (void)hipEventDestroy(g_ctx.ev_start);
   (void)hipEventDestroy(g_ctx.ev_stop);
   (void)hipStreamDestroy(g_ctx.stream);

@@ -766,6 +766,54 @@ class SeriesBatch:
         return _aggr_histogram_fetch(lib, n_rows.value,
                                      getattr(self, "_last_n_grid", 0))
 
+    def aggr_count_values(self, group_of, n_groups, max_rows_per_group):
+        """count_values() aggregate over the resident output of the last
+        ungrouped exec, on the device (csrc/aggrcv.hip); the rolled-up
+        matrix never leaves the device and is only read.  group_of and
+        n_groups as in aggr_histogram.  Within a group the members are
+        listed in ORIGINAL series order, also on a relayouted batch, so the
+        zero row's sign is the one aggregate.count_values finds first.
+        Returns (row_group u32[n_rows], row_value f64[n_rows], values
+        f64[n_rows, n_grid]) as engine.aggr_count_values does, and raises
+        as it does; VmGpuError after a grouped exec."""
+        _check_array("group_of", group_of, np.int32, 1)
+        n_groups = int(n_groups)
+        limit = _check_count_values_limit(max_rows_per_group)
+        if len(group_of) != self.n_series:
+            raise ValueError(f"group_of has {len(group_of)} entries for "
+                             f"{self.n_series} series")
+        if n_groups < 0 or (len(group_of) and (
+                group_of.min() < -1 or group_of.max() >= n_groups)):
+            raise ValueError("group_of entries must lie in [-1, n_groups)")
+        if getattr(self, "_last_grouped", False):
+            raise VmGpuError(
+                "aggr_count_values needs the output of an ungrouped exec; "
+                "the rows of the last exec are groups, not series")
+        perm = getattr(self, "_perm", None)
+        g_phys = group_of[perm] if perm is not None else group_of
+        rows = np.flatnonzero(g_phys >= 0)
+        orig = perm[rows] if perm is not None else rows
+        order = np.lexsort((orig, g_phys[rows]))  # by group, then original id
+        group_rows = np.ascontiguousarray(rows[order], dtype=np.uint32)
+        group_offsets = np.zeros(n_groups + 1, dtype=np.uint64)
+        np.cumsum(np.bincount(g_phys[rows], minlength=n_groups),
+                  out=group_offsets[1:])
+        lib = _load_lib()
+        init()
+        n_rows = ctypes.c_uint64(0)
+        errbuf = ctypes.create_string_buffer(256)
+        rc = lib.vmgpu_batch_aggr_count_values_exec(
+            ctypes.c_uint64(self.handle),
+            group_rows.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)),
+            group_offsets.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64)),
+            ctypes.c_uint32(n_groups), ctypes.c_uint32(limit),
+            ctypes.byref(n_rows), errbuf, ctypes.c_size_t(len(errbuf)))
+        if rc != 0:
+            raise _aggr_count_values_failed(
+                "vmgpu_batch_aggr_count_values_exec", rc, errbuf)
+        return _aggr_count_values_fetch(lib, n_rows.value,
+                                        getattr(self, "_last_n_grid", 0))
+
     def fetch_out_into(self, dst, n_grid):
         """Download the last exec's output rows directly into a caller
         buffer (e.g. a marshal buffer's values section) — no intermediate
@@ -1445,6 +1493,83 @@ def aggr_histogram(values, group_rows, group_offsets):
         raise VmGpuError(f"vmgpu_aggr_histogram_exec failed ({rc}): "
                          f"{errbuf.value.decode()}")
     return _aggr_histogram_fetch(lib, n_rows.value, n_grid)
+
+
+class CountValuesLimitError(VmGpuError):
+    """A group of aggr_count_values has more distinct values than
+    max_rows_per_group allows."""
+
+
+def _check_count_values_limit(max_rows_per_group):
+    limit = int(max_rows_per_group)
+    if not 1 <= limit <= 2 ** 24:
+        raise ValueError("max_rows_per_group must lie in [1, 2^24]")
+    return limit
+
+
+def _aggr_count_values_failed(what, rc, errbuf):
+    msg = errbuf.value.decode()
+    cls = CountValuesLimitError if "distinct values" in msg else VmGpuError
+    return cls(f"{what} failed ({rc}): {msg}")
+
+
+def _aggr_count_values_fetch(lib, n_rows, n_grid):
+    row_group = np.empty(n_rows, dtype=np.uint32)
+    row_value = np.empty(n_rows, dtype=np.float64)
+    values = np.empty((n_rows, n_grid), dtype=np.float64)
+    errbuf = ctypes.create_string_buffer(256)
+    rc = lib.vmgpu_aggr_count_values_fetch(
+        row_group.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)),
+        row_value.ctypes.data_as(ctypes.POINTER(ctypes.c_double)),
+        values.ctypes.data_as(ctypes.POINTER(ctypes.c_double)),
+        errbuf, ctypes.c_size_t(len(errbuf)))
+    if rc != 0:
+        raise VmGpuError(f"vmgpu_aggr_count_values_fetch failed ({rc}): "
+                         f"{errbuf.value.decode()}")
+    return row_group, row_value, values
+
+
+def aggr_count_values(values, group_rows, group_offsets, max_rows_per_group):
+    """count_values() aggregate (aggrFuncCountValues) over member rows per
+    group, on the device (csrc/aggrcv.hip: hash insert, row scan, sort,
+    count pass).  values f64[n_series, n_grid]; group g owns the rows
+    group_rows[group_offsets[g]:group_offsets[g + 1]] (u32 / u64).  The
+    output is sparse: one row per (group, distinct non-NaN value anywhere in
+    the group), -0.0 and 0.0 being one value, ordered by group and then by
+    ascending value.  Returns (row_group u32[n_rows], row_value
+    f64[n_rows], values f64[n_rows, n_grid]): the number of members equal to
+    the row's value, NaN where there is none.  The zero row's row_value has
+    the sign of the first zero in member order, then grid order.
+    max_rows_per_group in [1, 2^24] bounds the distinct values of one
+    group; beyond it CountValuesLimitError is raised and no result is left.
+    The arrays must already have these dtypes and be C-contiguous."""
+    _check_array("values", values, np.float64, 2)
+    _check_array("group_rows", group_rows, np.uint32, 1)
+    _check_array("group_offsets", group_offsets, np.uint64, 1)
+    limit = _check_count_values_limit(max_rows_per_group)
+    if len(group_offsets) < 1:
+        raise ValueError("group_offsets needs n_groups + 1 entries")
+    n_series, n_grid = values.shape
+    n_groups = len(group_offsets) - 1
+    if n_series >= 2 ** 32 or n_grid >= 2 ** 31 or n_groups >= 2 ** 32:
+        raise ValueError("matrix or group count beyond the C ABI's range")
+    if n_groups and int(group_offsets[-1]) > len(group_rows):
+        raise ValueError("group_offsets runs past the end of group_rows")
+    lib = _load_lib()
+    init()
+    n_rows = ctypes.c_uint64(0)
+    errbuf = ctypes.create_string_buffer(256)
+    rc = lib.vmgpu_aggr_count_values_exec(
+        values.ctypes.data_as(ctypes.POINTER(ctypes.c_double)),
+        ctypes.c_uint32(n_series), ctypes.c_int32(n_grid),
+        group_rows.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)),
+        group_offsets.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64)),
+        ctypes.c_uint32(n_groups), ctypes.c_uint32(limit),
+        ctypes.byref(n_rows), errbuf, ctypes.c_size_t(len(errbuf)))
+    if rc != 0:
+        raise _aggr_count_values_failed("vmgpu_aggr_count_values_exec", rc,
+                                        errbuf)
+    return _aggr_count_values_fetch(lib, n_rows.value, n_grid)
 
 
 def quantiles_over_time_plans(phi_label, phis, start, end, step, **kwargs):

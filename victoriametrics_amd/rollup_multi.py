@@ -276,7 +276,7 @@ _NAN_BITS = 0x7FF8000000000000
 
 def count_values_order_key(v):
     """The u64 by which the device orders (and tells apart) the values of
-    one series — host twin of cvot_order_key in csrc/cvot.hip.  On the
+    one series — host twin of cvot_order_key in csrc/value_key.h.  On the
     value's bits u, every NaN first mapped to 0x7FF8000000000000:
     (u >> 63) ? ~u : u | 1 << 63.  Unsigned-ascending is
     -Inf ... -0 < 0 ... +Inf < NaN; equal keys <=> equal 'g' labels."""
