@@ -42,4 +42,9 @@ build_one pipe_nosdesc -DVMGPU_PIPE_SDESC=0 &
 build_one pipe_noasmload -DVMGPU_PIPE_ASMLOAD=0 &
 build_one pipe_noprefetch -DVMGPU_PIPE_SDESC=0 -DVMGPU_PIPE_ASMLOAD=0 &
 wait
+# cuts found by the instruction account (profiles/pipe_probe_time.md), one
+# off at a time (all on by default)
+build_one pipe_noprobe1 -DVMGPU_PIPE_PROBE1=0 &
+build_one pipe_nodgonce -DVMGPU_PIPE_DG_ONCE=0 &
+wait
 echo "ablation libs built"

@@ -46,6 +46,7 @@
 
 #include "batch_access.h"
 #include "host_common.h"
+#include "pipe_probe.h"
 #include "rollup_device.h"
 #include "vm_div1e3.h"
 #include "../../include/vmgpu.h"
@@ -86,6 +87,24 @@
 #endif
 #ifndef VMGPU_PIPE_SKIP_PMAX
 #define VMGPU_PIPE_SKIP_PMAX 1
+#endif
+
+/* Cuts that came out of the instruction account of
+ * profiles/pipe_probe_time.md, gated the same way; none changes an output bit.
+ *   DG_ONCE  window / step (two 64-bit divisions, vector code even for
+ *            uniform operands) is computed once per wave and not once per
+ *            series: with a plan window it is the same for every series
+ *   PROBE1   the sentinel probe is the count form of pipe_probe.h: the four
+ *            records round the hint are read together and waited for once,
+ *            and the answer is a sum of compares, so its cost no longer
+ *            depends on how often the hint is right.  Needs SENTINEL; =0
+ *            keeps the select chain, which the compiler turns into up to
+ *            three dependent, exec-masked LDS trips */
+#ifndef VMGPU_PIPE_PROBE1
+#define VMGPU_PIPE_PROBE1 1
+#endif
+#ifndef VMGPU_PIPE_DG_ONCE
+#define VMGPU_PIPE_DG_ONCE 1
 #endif
 
 /* Latency cuts of the pipe kernel's series loop (profiles/pipe_prefetch.md),
@@ -219,8 +238,15 @@ static VM_DEV int64_t vm_uniform_i64(int64_t x) {
  * ts[n] = INT64_MAX, and the candidates g+1 > n and g-1 < 0 fail on the
  * same records (INT64_MAX <= seek resp. INT64_MIN > seek are false).  A
  * seek of INT64_MAX itself ends in the binary-search fallback like any other
- * miss.  Result identical to vm_upper_bound<2>. */
+ * miss.  Result identical to vm_upper_bound<2>.
+ * The default (VMGPU_PIPE_PROBE1) is the same decision written as a count in
+ * pipe_probe.h, which re-derives these edge cases for that form. */
 static VM_DEV int vm_ub_hint_sent(const int64_t* ts, int n, int64_t seek, int g) {
+#if VMGPU_PIPE_PROBE1
+  /* count form: one LDS trip, no tier that runs only for the lanes whose
+   * hint missed (derivation in pipe_probe.h) */
+  int r = vm_probe_count4(ts, n, seek, g);
+#else
   g = g < 0 ? 0 : (g > n ? n : g);
   const int64_t* b = ts + (g - 2) * 2;
   int64_t t_m2 = b[0];
@@ -234,6 +260,7 @@ static VM_DEV int vm_ub_hint_sent(const int64_t* ts, int n, int64_t seek, int g)
   bool ok_p1 = (t_0 <= seek) & (t_p1 > seek);
   bool ok_m1 = (t_m2 <= seek) & (t_m1 > seek);
   int r = ok_g ? g : (ok_p1 ? g + 1 : (ok_m1 ? g - 1 : -1));
+#endif
   if (__any(r < 0)) {
     if (r < 0) r = vm_upper_bound<2>(ts, n, seek);
   }
@@ -1687,6 +1714,16 @@ void rollup_pipe_kernel(KPlan p, KIO io) {
    *     on the hot path waits on vmcnt: no drain before the prefetch issue
    *     and none at the back edge. */
   uint32_t ws = __builtin_amdgcn_readfirstlane(wave_id);
+#if VMGPU_PIPE_DG_ONCE
+  /* window / step in grid points.  The host launches this kernel only with a
+   * plan window, which series_window() hands back unchanged for every series,
+   * so the two 64-bit divisions are done once per wave here and not once per
+   * series in the loop (the instruction account of
+   * profiles/pipe_probe_time.md found them there). */
+  [[maybe_unused]] const int dg_plan = __builtin_amdgcn_readfirstlane(
+      (p.window > 0 && p.step > 0 && p.window % p.step == 0)
+          ? (int)(p.window / p.step) : 0);
+#endif
   PipeDesc cur = {0, 0, 0, 0, -1};
   PipeDesc nxt = {0, 0, 0, 0, -1};
   uint32_t s_nn = 0;
@@ -1881,8 +1918,15 @@ void rollup_pipe_kernel(KPlan p, KIO io) {
     if constexpr (FUNC_CT == VMF_RATE || FUNC_CT == VMF_DERIV_FAST) {
       const bool dt32 = VMGPU_PIPE_DT_FAST != 0;
       const bool dt_ok = dt32_series || !dt32;
+#if VMGPU_PIPE_DG_ONCE
+      /* with a plan window, sw.window is that window for every series */
+      int dg64 = p.window > 0 ? dg_plan
+                 : ((sw.window > 0 && p.step > 0 && sw.window % p.step == 0)
+                        ? (int)(sw.window / p.step) : 0);
+#else
       int dg64 = (sw.window > 0 && p.step > 0 && sw.window % p.step == 0)
                      ? (int)(sw.window / p.step) : 0;
+#endif
       if (dt_ok && p.jbuf_mode >= 1 &&
           (size_t)p.n_grid * 2 <= vm_jbuf_bytes(p.jbuf_mode, p.jbuf_elems) &&
           dg64 > 0 && count <= 65535) {
