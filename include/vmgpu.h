@@ -581,6 +581,57 @@ int vmgpu_batch_aggr_count_values_exec(uint64_t handle,
 int vmgpu_aggr_count_values_fetch(uint32_t* row_group, double* row_value,
                                   double* out, char* errbuf, size_t errbuf_len);
 
+/* Grouped pointwise topk / bottomk (`topk(k, q) by (...)`, newAggrFuncTopK,
+ * aggr.go:646-675) over the rows of a [n_series x n_grid] matrix, grouped by
+ * the member CSR of the histogram() aggregate above.  Every (group, grid
+ * column c) is handled on its own.  The group's members are numbered
+ * p = 0..n-1 in CSR order.  kn = getIntK(ks[c], n) of them are kept (NaN and
+ * negative k give 0, k is truncated toward zero, saturates from 2^63 and is
+ * clamped to n): the kn largest under the composite order (value key, then
+ * p), where the value key orders the values ascending (reverse = 0, topk) or
+ * descending (reverse != 0, bottomk), -0.0 and +0.0 are equal, and every
+ * NaN, the stale NaN included, is smaller than every number in both
+ * directions and is never kept.  Of equal values the member LATER in the
+ * group's member list wins.  The result is a pure function of the input: the
+ * same input gives the same bits on every run.
+ *   The output is SPARSE: one row per member position that keeps at least
+ * one non-NaN value, ordered by group and then by member position.  A row
+ * listed in two groups is two members and can give two output rows.  A kept
+ * cell carries the input's own bits (a kept -0.0 stays -0.0); every other
+ * cell of an output row is the canonical NaN 0x7FF8000000000000.  The input
+ * matrix is never written.
+ *
+ * vmgpu_aggr_topk_exec: values is a HOST matrix, uploaded for the call.
+ * vmgpu_batch_aggr_topk_exec: the matrix is the resident output of the
+ *   batch's last ungrouped vmgpu_rollup_exec, which never leaves the device
+ *   and is only read; group_rows are PHYSICAL output rows.  A batch without a
+ *   last output is an error.
+ *   ks[n_ks] holds one k per grid column.  Both forms return the row count,
+ *   report their kernel time through vmgpu_last_kernel_ms and leave the
+ *   result resident in the library context, replacing the earlier one
+ *   (vmgpu_shutdown frees it).  Errors, all before any kernel is launched:
+ *   the CSR and grid errors of vmgpu_aggr_histogram_exec, ks == NULL,
+ *   n_ks != n_grid, members x n_grid or groups x n_grid x 16 bytes beyond 63
+ *   bits.  Zero groups or zero members give 0 rows and launch nothing.  A
+ *   failed call leaves no result.
+ * vmgpu_aggr_topk_fetch: downloads the last result of either exec:
+ *   row_group[n_rows], row_src[n_rows] (the input matrix row
+ *   group_rows[member]; in the batch form the PHYSICAL row), row_last[n_rows]
+ *   (the member's INPUT value in the last grid column, kept or not: what the
+ *   reference's final sort orders the series by) and out[n_rows x n_grid].
+ *   Any destination may be NULL.  Without a valid result it is an error. */
+int vmgpu_aggr_topk_exec(const double* values, uint32_t n_series, int32_t n_grid,
+                         const uint32_t* group_rows, const uint64_t* group_offsets,
+                         uint32_t n_groups, const double* ks, uint32_t n_ks,
+                         int32_t reverse, uint64_t* out_n_rows,
+                         char* errbuf, size_t errbuf_len);
+int vmgpu_batch_aggr_topk_exec(uint64_t handle, const uint32_t* group_rows,
+                               const uint64_t* group_offsets, uint32_t n_groups,
+                               const double* ks, uint32_t n_ks, int32_t reverse,
+                               uint64_t* out_n_rows, char* errbuf, size_t errbuf_len);
+int vmgpu_aggr_topk_fetch(uint32_t* row_group, uint32_t* row_src, double* row_last,
+                          double* out, char* errbuf, size_t errbuf_len);
+
 /* Pinned host buffers for PCIe-rate staging of payloads and results (the
  * cgo layer would pool these; hipHostMalloc/-Free underneath). */
 int vmgpu_host_alloc(uint64_t nbytes, void** out_ptr);

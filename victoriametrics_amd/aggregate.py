@@ -27,7 +27,15 @@ on the GPU:
   (csrc/aggrcv.hip: per-group hash insert / row scan / sort / count over
   the same member CSR) and count_values_batch over a SeriesBatch's resident
   rollup output.  One row per distinct value of a group, at most
-  max_series_per_aggr of them; naming stays on the host.
+  max_series_per_aggr of them; naming stays on the host;
+- grouped topk/bottomk on the device: topk_device runs the per-point
+  selection of aggregate("topk" / "bottomk") through engine.aggr_topk
+  (csrc/aggrtopk.hip: per (group, column) threshold / mark / row scan / fill
+  over the same member CSR, per-point k, ties to the later member as in the
+  oracle) and topk_batch over a SeriesBatch's resident rollup output, of
+  which only the rows that keep a value come back.  Both return new Series
+  and leave their input alone.  aggregate("topk") is not routed there yet;
+  the range families and outliersk stay on the host.
 
 This layer exists for aggregation over RESIDENT result series (e.g. after
 binary ops or transforms).  The rollup->aggregate hot path keeps using the
@@ -392,6 +400,90 @@ def _pointwise_topk(groups, ks, is_reverse):
         tss.reverse()
         rvs.extend(tss)
     return rvs
+
+
+def _topk_rows_to_series(member_mns, row_group, row_member, row_last, values,
+                         reverse=False):
+    """One Series per sparse device row of the grouped topk, as the
+    reference's topk returns them: kept members carry their ORIGINAL metric
+    name (member_mns[row_member[i]]; topk is keepOriginal), groups come in
+    grouping order (row_group ascending, as the device lists them) and inside
+    a group the rows come best-first by row_last, the member's input value
+    in the last column, under the direction's order, NaN last; ties go by
+    descending member position.  That is the reference's final sort plus
+    reverseSeries; its tie order is open."""
+    n_rows = len(row_group)
+    keyf = _greater_with_nans_key if reverse else _less_with_nans_key
+    # rows arrive ordered by (group, member position): sort ascending under
+    # the direction's order, stable, then reverse the group's run, so equal
+    # values end up in descending position
+    order = []
+    i = 0
+    while i < n_rows:
+        j = i
+        while j < n_rows and row_group[j] == row_group[i]:
+            j += 1
+        run = sorted(range(i, j), key=lambda r: keyf(float(row_last[r])))
+        run.reverse()
+        order.extend(run)
+        i = j
+    return [Series(member_mns[int(row_member[r])].copy(), values[r].copy())
+            for r in order]
+
+
+def topk_device(series, k, modifier_op="", modifier_args=(), limit=0,
+                reverse=False):
+    """aggregate("topk" / "bottomk") with the groups x grid points x members
+    loop on the device (engine.aggr_topk, csrc/aggrtopk.hip).  k is a scalar
+    or one value per grid point.  Same kept values per group and grid point
+    as the host path wherever the reference defines them; where several
+    members tie at the boundary the later member is kept (the oracle's
+    rule).  Unlike the host path the input Series are not mutated: the
+    result holds new arrays."""
+    groups = prepare_series(series, modifier_op, modifier_args, limit,
+                            keep_original=True)
+    if not groups:
+        return []
+    v, gr, go = _matrix(groups)
+    row_group, row_src, row_last, values = engine.aggr_topk(
+        np.ascontiguousarray(v, dtype=np.float64), gr, go, k, reverse)
+    member_mns = [s.mn for _, members in groups for s in members]
+    return _topk_rows_to_series(member_mns, row_group, row_src, row_last,
+                                values, reverse)
+
+
+def topk_batch(batch, metric_names, k, modifier_op="", modifier_args=(),
+               limit=0, reverse=False):
+    """topk / bottomk over the resident output of a SeriesBatch's last
+    ungrouped exec: the rolled-up matrix stays on the device
+    (SeriesBatch.aggr_topk) and only the rows that keep a value come back.
+    metric_names[s] names ORIGINAL series s as the rollup left it; the
+    grouping comes from those names, the members of a group stand in
+    original series order.
+
+    A series whose output row is all NaN stays in its group: it keeps
+    nothing and creates no row, so the result is that of topk_device, which
+    drops such series first (remove_empty_series).  The one visible
+    difference: with limit > 0 a group whose members are ALL empty still
+    takes one of the limit's slots here."""
+    m = {}
+    n_groups = 0
+    group_of = np.full(len(metric_names), -1, dtype=np.int32)
+    for s, name in enumerate(metric_names):
+        mn = name.copy()
+        remove_group_tags(mn, modifier_op, modifier_args)
+        key = mn.marshal_sorted()
+        g = m.get(key)
+        if g is None:
+            if limit > 0 and len(m) >= limit:
+                continue
+            g = m[key] = n_groups
+            n_groups += 1
+        group_of[s] = g
+    row_group, row_src, row_last, values = batch.aggr_topk(
+        group_of, n_groups, k, reverse)
+    return _topk_rows_to_series(metric_names, row_group, row_src, row_last,
+                                values, reverse)
 
 
 def _per_point_medians(tss):

@@ -2,7 +2,9 @@
  * (histogram()) and aggrcv.hip (count_values()) both cut every group into
  * chunks of members, hand (chunk, tile of 64 columns) work items to
  * wavefronts, count into a zeroed u32 matrix and convert it to f64 at the
- * end.  Only the row discovery differs.  The library is built without
+ * end.  Only the row discovery differs.  aggrtopk.hip (grouped topk) takes
+ * the chunk list, the work items and the CSR checks from here and counts
+ * nothing.  The library is built without
  * relocatable device code, so the kernel here is instantiated per file. */
 #ifndef VMGPU_AGGR_SPARSE_H
 #define VMGPU_AGGR_SPARSE_H

@@ -1,6 +1,7 @@
 /* Narrow internal window onto a resident batch for entry points that live
- * outside vmgpu.hip (hot.hip, cvot.hip, topk.hip, aggrhist.hip, aggrcv.hip;
- * hstat.hip takes only the context lock from here).  Batch itself stays private.  Same spirit as
+ * outside vmgpu.hip (hot.hip, cvot.hip, topk.hip, aggrhist.hip, aggrcv.hip,
+ * aggrtopk.hip; hstat.hip takes only the context lock from here).  Batch
+ * itself stays private.  Same spirit as
  * vm_ctx_stream (devalloc.h): the caller runs on the context stream and
  * holds the context lock for as long as it uses what it got here. */
 #ifndef VMGPU_BATCH_ACCESS_H
@@ -96,5 +97,8 @@ void vm_aggrhist_shutdown(void);
 
 /* aggrcv.hip: the same for the count_values() aggregate */
 void vm_aggrcv_shutdown(void);
+
+/* aggrtopk.hip: the same for the grouped topk / bottomk aggregate */
+void vm_aggrtopk_shutdown(void);
 
 #endif

@@ -18,7 +18,7 @@ build_one() {
   name=$1
   shift
   hipcc $FLAGS "$@" -shared vmgpu.hip decode.hip binop.hip transform.hip aggrcol.hip hot.hip cvot.hip \
-    topk.hip hstat.hip aggrhist.hip aggrcv.hip -o ../libvmgpu_$name.so
+    topk.hip hstat.hip aggrhist.hip aggrcv.hip aggrtopk.hip -o ../libvmgpu_$name.so
 }
 
 build_one pipe_stage -DVMGPU_PIPE_ABL_STAGE &

@@ -1,6 +1,7 @@
 /* Rows keyed on a double's value: the order key, the bitonic sort and the
  * search that cvot.hip (count_values_over_time, per series) and aggrcv.hip
- * (the count_values() aggregate, per group) share.
+ * (the count_values() aggregate, per group) share.  aggrtopk.hip (grouped
+ * topk) uses the sort and the size classes with a key of its own.
  *
  * Order key of value bits u (all NaNs first folded to HOT_NAN_BITS):
  *   (u >> 63) ? ~u : u | 1 << 63

@@ -1928,6 +1928,7 @@ int vmgpu_shutdown(void) {
   vm_hot_shutdown();
   vm_aggrhist_shutdown();
   vm_aggrcv_shutdown();
+  vm_aggrtopk_shutdown();
   (void)hipEventDestroy(g_ctx.ev_start);
   (void)hipEventDestroy(g_ctx.ev_stop);
   (void)hipStreamDestroy(g_ctx.stream);

@@ -814,6 +814,61 @@ class SeriesBatch:
         return _aggr_count_values_fetch(lib, n_rows.value,
                                         getattr(self, "_last_n_grid", 0))
 
+    def aggr_topk(self, group_of, n_groups, k, reverse=False):
+        """Grouped pointwise topk (bottomk with reverse=True) over the
+        resident output of the last ungrouped exec, on the device
+        (csrc/aggrtopk.hip); the rolled-up matrix never leaves the device
+        and is only read.  group_of and n_groups as in aggr_histogram; k is
+        a scalar or one value per grid column.  Within a group the members
+        are listed in ORIGINAL series order, also on a relayouted batch, so
+        ties fall as they do for engine.aggr_topk over the downloaded
+        output.  Returns (row_group, row_src, row_last, values) as
+        engine.aggr_topk does, with row_src mapped back to ORIGINAL series
+        ids.  Raises VmGpuError after a grouped exec."""
+        _check_array("group_of", group_of, np.int32, 1)
+        n_groups = int(n_groups)
+        if len(group_of) != self.n_series:
+            raise ValueError(f"group_of has {len(group_of)} entries for "
+                             f"{self.n_series} series")
+        if n_groups < 0 or (len(group_of) and (
+                group_of.min() < -1 or group_of.max() >= n_groups)):
+            raise ValueError("group_of entries must lie in [-1, n_groups)")
+        n_grid = getattr(self, "_last_n_grid", 0)
+        ks = _check_topk_ks(k, n_grid)
+        if getattr(self, "_last_grouped", False):
+            raise VmGpuError(
+                "aggr_topk needs the output of an ungrouped exec; the rows "
+                "of the last exec are groups, not series")
+        perm = getattr(self, "_perm", None)
+        g_phys = group_of[perm] if perm is not None else group_of
+        rows = np.flatnonzero(g_phys >= 0)
+        orig = perm[rows] if perm is not None else rows
+        order = np.lexsort((orig, g_phys[rows]))  # by group, then original id
+        group_rows = np.ascontiguousarray(rows[order], dtype=np.uint32)
+        group_offsets = np.zeros(n_groups + 1, dtype=np.uint64)
+        np.cumsum(np.bincount(g_phys[rows], minlength=n_groups),
+                  out=group_offsets[1:])
+        lib = _load_lib()
+        init()
+        n_rows = ctypes.c_uint64(0)
+        errbuf = ctypes.create_string_buffer(256)
+        rc = lib.vmgpu_batch_aggr_topk_exec(
+            ctypes.c_uint64(self.handle),
+            group_rows.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)),
+            group_offsets.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64)),
+            ctypes.c_uint32(n_groups),
+            ks.ctypes.data_as(ctypes.POINTER(ctypes.c_double)),
+            ctypes.c_uint32(len(ks)), ctypes.c_int32(1 if reverse else 0),
+            ctypes.byref(n_rows), errbuf, ctypes.c_size_t(len(errbuf)))
+        if rc != 0:
+            raise VmGpuError(f"vmgpu_batch_aggr_topk_exec failed ({rc}): "
+                             f"{errbuf.value.decode()}")
+        row_group, row_src, row_last, values = _aggr_topk_fetch(
+            lib, n_rows.value, n_grid)
+        if perm is not None:
+            row_src = np.asarray(perm, dtype=np.uint32)[row_src]
+        return row_group, row_src, row_last, values
+
     def fetch_out_into(self, dst, n_grid):
         """Download the last exec's output rows directly into a caller
         buffer (e.g. a marshal buffer's values section) — no intermediate
@@ -1570,6 +1625,80 @@ def aggr_count_values(values, group_rows, group_offsets, max_rows_per_group):
         raise _aggr_count_values_failed("vmgpu_aggr_count_values_exec", rc,
                                         errbuf)
     return _aggr_count_values_fetch(lib, n_rows.value, n_grid)
+
+
+def _check_topk_ks(k, n_grid):
+    """k of aggr_topk: a scalar or one value per grid column, as f64."""
+    ks = np.asarray(k, dtype=np.float64)
+    if ks.ndim > 1:
+        raise ValueError("k must be a scalar or a 1-d array")
+    if ks.ndim == 1 and len(ks) != n_grid:
+        raise ValueError(f"k has {len(ks)} entries for {n_grid} grid points")
+    return np.ascontiguousarray(np.broadcast_to(ks, (n_grid,)))
+
+
+def _aggr_topk_fetch(lib, n_rows, n_grid):
+    row_group = np.empty(n_rows, dtype=np.uint32)
+    row_src = np.empty(n_rows, dtype=np.uint32)
+    row_last = np.empty(n_rows, dtype=np.float64)
+    values = np.empty((n_rows, n_grid), dtype=np.float64)
+    errbuf = ctypes.create_string_buffer(256)
+    rc = lib.vmgpu_aggr_topk_fetch(
+        row_group.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)),
+        row_src.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)),
+        row_last.ctypes.data_as(ctypes.POINTER(ctypes.c_double)),
+        values.ctypes.data_as(ctypes.POINTER(ctypes.c_double)),
+        errbuf, ctypes.c_size_t(len(errbuf)))
+    if rc != 0:
+        raise VmGpuError(f"vmgpu_aggr_topk_fetch failed ({rc}): "
+                         f"{errbuf.value.decode()}")
+    return row_group, row_src, row_last, values
+
+
+def aggr_topk(values, group_rows, group_offsets, k, reverse=False):
+    """Grouped pointwise topk (bottomk with reverse=True) over member rows
+    per group, on the device (csrc/aggrtopk.hip: threshold, mark, row scan,
+    fill).  values f64[n_series, n_grid]; group g owns the rows
+    group_rows[group_offsets[g]:group_offsets[g + 1]] (u32 / u64), numbered
+    p = 0..n-1 in that order.  k is a scalar or one value per grid column.
+    Per (group, column) the getIntK(k, n) largest members under (value, then
+    p) are kept: of equal values the later member wins, -0.0 equals 0.0, a
+    NaN is never kept.  The output is sparse: one row per member that keeps
+    at least one value, ordered by group and then by p.  Returns (row_group
+    u32[n_rows], row_src u32[n_rows] the row of values, row_last f64[n_rows]
+    the member's input value in the last column, values f64[n_rows, n_grid]
+    with the input's bits where kept and NaN elsewhere).  values is not
+    written.  The arrays must already have these dtypes and be
+    C-contiguous."""
+    _check_array("values", values, np.float64, 2)
+    _check_array("group_rows", group_rows, np.uint32, 1)
+    _check_array("group_offsets", group_offsets, np.uint64, 1)
+    if len(group_offsets) < 1:
+        raise ValueError("group_offsets needs n_groups + 1 entries")
+    n_series, n_grid = values.shape
+    n_groups = len(group_offsets) - 1
+    if n_series >= 2 ** 32 or n_grid >= 2 ** 31 or n_groups >= 2 ** 32:
+        raise ValueError("matrix or group count beyond the C ABI's range")
+    if n_groups and int(group_offsets[-1]) > len(group_rows):
+        raise ValueError("group_offsets runs past the end of group_rows")
+    ks = _check_topk_ks(k, n_grid)
+    lib = _load_lib()
+    init()
+    n_rows = ctypes.c_uint64(0)
+    errbuf = ctypes.create_string_buffer(256)
+    rc = lib.vmgpu_aggr_topk_exec(
+        values.ctypes.data_as(ctypes.POINTER(ctypes.c_double)),
+        ctypes.c_uint32(n_series), ctypes.c_int32(n_grid),
+        group_rows.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)),
+        group_offsets.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64)),
+        ctypes.c_uint32(n_groups),
+        ks.ctypes.data_as(ctypes.POINTER(ctypes.c_double)),
+        ctypes.c_uint32(len(ks)), ctypes.c_int32(1 if reverse else 0),
+        ctypes.byref(n_rows), errbuf, ctypes.c_size_t(len(errbuf)))
+    if rc != 0:
+        raise VmGpuError(f"vmgpu_aggr_topk_exec failed ({rc}): "
+                         f"{errbuf.value.decode()}")
+    return _aggr_topk_fetch(lib, n_rows.value, n_grid)
 
 
 def quantiles_over_time_plans(phi_label, phis, start, end, step, **kwargs):
