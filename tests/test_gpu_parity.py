@@ -36,7 +36,7 @@ ARG_FUNCS = {
     "share_gt_over_time": 5.0, "share_eq_over_time": 1.0,
     "sum_le_over_time": 5.0, "sum_gt_over_time": 5.0,
     "sum_eq_over_time": 1.0, "predict_linear": 120.0,
-    "duration_over_time": 60.0, "quantile_over_time": 0.9,
+    "duration_over_time": 60.0,
     "hoeffding_bound_lower": 0.9, "hoeffding_bound_upper": 0.9,
     "holt_winters": 0.3,
 }

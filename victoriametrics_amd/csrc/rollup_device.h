@@ -97,14 +97,15 @@ static VM_DEV double vm_dev_quantile(double phi, const double* v, int n) {
   return lo * (1 - weight) + hi * weight;
 }
 
-/* k-th smallest of |v[i]-med| (for MAD), NaN-skipping. */
+/* k-th smallest of |v[i]-med| (for MAD), NaN-skipping.  The deviation is
+ * NaN where v[i] is, and also where v[i] and med are the same infinity; the
+ * reference's quantile() drops both from the deviations (aggr.go:870-890). */
 static VM_DEV double vm_select_kth_absdev(const double* v, int n, double med, int k) {
   for (int c = 0; c < n; c++) {
-    if (vm_isnan(v[c])) continue;
     double x = fabs(v[c] - med);
+    if (vm_isnan(x)) continue;
     int less = 0, eq = 0;
     for (int i = 0; i < n; i++) {
-      if (vm_isnan(v[i])) continue;
       double y = fabs(v[i] - med);
       if (y < x) less++;
       else if (y == x) eq++;
@@ -117,7 +118,7 @@ static VM_DEV double vm_select_kth_absdev(const double* v, int n, double med, in
 static VM_DEV double vm_dev_quantile_absdev(double phi, const double* v, int n, double med) {
   int m = 0;
   for (int i = 0; i < n; i++)
-    if (!vm_isnan(v[i])) m++;
+    if (!vm_isnan(fabs(v[i] - med))) m++;
   if (m == 0 || vm_isnan(phi)) return vm_dnan();
   double nn = (double)m;
   double rank = phi * (nn - 1);
