@@ -68,14 +68,20 @@ void vm_colagg(int32_t op, const double* values, uint32_t n_series,
         case 2: { /* mad */
           int cnt = ca_sorted_col(values, n_grid, group_rows, lo, hi, g, sc);
           double med = ca_quantile_sorted(0.5, sc, cnt);
-          for (int i = 0; i < cnt; i++) sc[i] = fabs(sc[i] - med);
-          for (int i = 1; i < cnt; i++) {
+          /* quantile() drops NaN before it sorts: with an infinite median
+           * the deviation of every sample equal to it is NaN and leaves */
+          int dcnt = 0;
+          for (int i = 0; i < cnt; i++) {
+            double d = fabs(sc[i] - med);
+            if (!isnan(d)) sc[dcnt++] = d;
+          }
+          for (int i = 1; i < dcnt; i++) {
             double v = sc[i];
             int j = i;
             while (j > 0 && sc[j - 1] > v) { sc[j] = sc[j - 1]; j--; }
             sc[j] = v;
           }
-          out[e] = ca_quantile_sorted(0.5, sc, cnt);
+          out[e] = ca_quantile_sorted(0.5, sc, dcnt);
           break;
         }
         case 3:   /* stddev */

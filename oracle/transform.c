@@ -408,14 +408,20 @@ int32_t vm_tf_series(int32_t func, double* row, int64_t n, const int64_t* ts,
     double* sc = (double*)malloc((size_t)(n > 0 ? n : 1) * 8);
     int cnt = tf_sorted_nonnan(row, n, sc);
     double med = tf_quantile_sorted(0.5, sc, cnt);
-    for (int i = 0; i < cnt; i++) sc[i] = fabs(sc[i] - med);
-    for (int i = 1; i < cnt; i++) {
+    /* quantile() drops NaN before it sorts: with an infinite median the
+     * deviation of every sample equal to it is NaN and leaves */
+    int dcnt = 0;
+    for (int i = 0; i < cnt; i++) {
+      double d = fabs(sc[i] - med);
+      if (!isnan(d)) sc[dcnt++] = d;
+    }
+    for (int i = 1; i < dcnt; i++) {
       double v = sc[i];
       int j = i;
       while (j > 0 && sc[j - 1] > v) { sc[j] = sc[j - 1]; j--; }
       sc[j] = v;
     }
-    double madv = tf_quantile_sorted(0.5, sc, cnt);
+    double madv = tf_quantile_sorted(0.5, sc, dcnt);
     if (func == TF_RANGE_MAD) {
       for (int64_t i = 0; i < n; i++) row[i] = madv;
     } else {

@@ -2,6 +2,7 @@
 transcribed from aggr_test.go TestModeNoNaNs; hand-derived quantile/mad/
 share/zscore cases from aggr.go) — CPU side."""
 import math
+import zlib
 
 import numpy as np
 import pytest
@@ -149,7 +150,7 @@ def test_multi_group_multi_point():
                                 "stdvar", "mode", "distinct"])
 def test_gpu_colagg_reduce(op):
     from victoriametrics_amd import engine
-    rng = np.random.default_rng(abs(hash(op)) % 2**31)
+    rng = np.random.default_rng(zlib.crc32(op.encode()))
     n_series, n_grid, n_groups = 300, 120, 23
     v = rng.standard_normal((n_series, n_grid)) * 50
     v[rng.random((n_series, n_grid)) < 0.2] = NAN
@@ -172,7 +173,7 @@ def test_gpu_colagg_reduce(op):
 @pytest.mark.parametrize("op", ["share", "zscore"])
 def test_gpu_colagg_per_series(op):
     from victoriametrics_amd import engine
-    rng = np.random.default_rng(abs(hash(op)) % 2**31)
+    rng = np.random.default_rng(zlib.crc32(op.encode()))
     n_series, n_grid = 200, 80
     v = rng.standard_normal((n_series, n_grid)) * 10
     v[rng.random((n_series, n_grid)) < 0.25] = NAN

@@ -3,6 +3,7 @@ pair kernel over all 18 ops (+ bool modifier, fills, dropNaNRight), the
 set-op mask kernel, the `or` merge-walk kernel, and the full host dispatch
 run GPU-vs-oracle on identical inputs."""
 import math
+import zlib
 
 import numpy as np
 import pytest
@@ -48,7 +49,7 @@ def _assert_op_equal(op, got, exp, msg):
 def test_pairs_kernel_all_ops(op, is_bool):
     if is_bool and op not in ("==", "!=", ">", "<", ">=", "<="):
         pytest.skip("bool modifier only applies to comparisons")
-    rng = np.random.default_rng(hash(op) % 2**31)
+    rng = np.random.default_rng(zlib.crc32(op.encode()))
     n_pairs, n_grid = 37, 240
     a = np.stack([_rand(rng, n_grid) for _ in range(n_pairs)])
     b = np.stack([_rand(rng, n_grid) for _ in range(n_pairs)])

@@ -420,15 +420,21 @@ __global__ void transform_series_kernel(int func, double* values,
         int cnt = t_sorted_nonnan(row, n, sc);
         double med = t_quantile_sorted(0.5, sc, cnt);
         /* mad (rollup.go:1476): median of |v - med| */
-        for (int i = 0; i < cnt; i++) sc[i] = fabs(sc[i] - med);
+        /* quantile() drops NaN before it sorts: with an infinite median
+         * the deviation of every sample equal to it is NaN and leaves */
+        int dcnt = 0;
+        for (int i = 0; i < cnt; i++) {
+          double d = fabs(sc[i] - med);
+          if (!isnan(d)) sc[dcnt++] = d;
+        }
         /* re-sort the deviations */
-        for (int i = 1; i < cnt; i++) {
+        for (int i = 1; i < dcnt; i++) {
           double v = sc[i];
           int j = i;
           while (j > 0 && sc[j - 1] > v) { sc[j] = sc[j - 1]; j--; }
           sc[j] = v;
         }
-        double madv = t_quantile_sorted(0.5, sc, cnt);
+        double madv = t_quantile_sorted(0.5, sc, dcnt);
         if (func == VMGPU_TF_RANGE_MAD) {
           for (uint32_t i = 0; i < n; i++) row[i] = madv;
         } else {
